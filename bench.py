@@ -2,9 +2,15 @@
 """bench.py -- perft leaf nodes/s (headline) + validated moves/s on MI355X.
 
 Contract (see README / DESIGN.md):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N>1: launched by torch.distributed.run, one rank per GPU; RCCL ("nccl") for
   the per-root-move all-reduce of leaf counts and the max-over-ranks timing.
+  A plain run times the headline only: W warm-up steps, K timed steps, the
+  result line.  --dump-outputs DIR writes the last timed step's result
+  (divide.npy, n_root.npy, total.npy; float64, exact) for output-for-output
+  comparison of two builds.  --full adds every other leg described below
+  (secondary objects of the line, per-kernel profile and roofline, CPU
+  baselines); --only LEGS and --profile-only select among them and imply it.
 
 Workload: perft(startpos, 7) under RULES_REF -- the reference validator's own
 rules (core/src/chess.rs), bit-exact -- with the frontier at ply 3 split into
@@ -85,7 +91,14 @@ def parse():
                     help="contexts a repeated perft's steps are split over (0: 3 at depth <= 6, 2 at 7, 1 deeper)")
     ap.add_argument("--suite-batch-only", action="store_true",
                     help="FIDE suite leg: the batch alone, no per-position runs (its PMC pass: one kind of dispatch)")
-    ap.add_argument("--only", default="", help="comma-separated legs to run (rocprof passes): " + ", ".join(LEGS))
+    ap.add_argument("--only", default="", help="comma-separated legs to run (rocprof passes; implies --full): "
+                    + ", ".join(LEGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, run every other leg too (per-kernel profile and roofline, "
+                         "one-stream figures, perft 6/8/9, FIDE, replay, state hash, signatures, latency, CPU "
+                         "baselines); --only and --profile-only select among these legs and imply it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed headline step returned (divide, n_root, total) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -260,7 +273,7 @@ def enqueue_split(engs, steps, base_ptr, W, fn):
         e.synchronize()
 
 
-def timed_perft(eng, d, args, pos, depth, steps, warmup, rules=dchess.RULES_REF, want=None, streams=None):
+def timed_perft(eng, d, args, pos, depth, steps, warmup, rules=dchess.RULES_REF, want=None, streams=None, keep=None):
     """warmup + exactly `steps` timed perft(depth) steps (barrier + device sync on
     both sides, max over ranks), parity-checked against the golden count.
 
@@ -270,7 +283,8 @@ def timed_perft(eng, d, args, pos, depth, steps, warmup, rules=dchess.RULES_REF,
     the exchange step -- the all-reduce of each step's per-root-move vector --
     runs over RCCL on the device, bucketed into one collective after the last
     step (K x 258 x 8 B instead of K tiny ones); the reduced totals are checked
-    after the timed region."""
+    after the timed region.  `keep` (a dict) receives the last timed step's
+    result record under "last" (--dump-outputs)."""
     if want is None and rules == dchess.RULES_REF:
         want = REF_STARTPOS.get(depth)
     for _ in range(warmup):  # host path: also captures the launch graph for this shard
@@ -331,7 +345,19 @@ def timed_perft(eng, d, args, pos, depth, steps, warmup, rules=dchess.RULES_REF,
         raise SystemExit(f"perft({depth}) overflowed its level buffers in the timed region")
     if want is not None and not (totals == want).all():
         raise SystemExit(f"parity failure in timed region: {totals.tolist()} != {want}")
+    if keep is not None:
+        keep["last"] = np.array(res[steps - 1], np.uint64)
     return int(totals.sum(dtype=np.uint64)), dt
+
+
+def dump_outputs(path, rec):
+    """--dump-outputs: the last timed step's result record (what a caller of
+    dc_perft_repeat_device reads back: divide[256], n_root, total) as float64
+    .npy files; every count is below 2^53, so the conversion is exact."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "divide.npy"), rec[:256].astype(np.float64))
+    np.save(os.path.join(path, "n_root.npy"), (rec[256:257] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "total.npy"), rec[257:258].astype(np.float64))
 
 
 def profiled_perft(eng, d, args, pos, depth, steps):
@@ -1012,6 +1038,9 @@ def main():
         if bad:
             raise SystemExit(f"--only: unknown legs {sorted(bad)} (known: {', '.join(LEGS)})")
         args.profile_only = True
+    elif not (args.full or args.profile_only):
+        # the plain run: set up, warm up, time the headline steps, print the line
+        legs = {"perft"}
     else:
         legs = set(LEGS)
         if args.no_perft:
@@ -1028,6 +1057,9 @@ def main():
             legs -= {"tx"}
         if args.depth == 6:
             legs -= {"perft6"}
+    full = bool(args.full or args.profile_only)  # --only has set profile_only
+    if args.dump_outputs and "perft" not in legs:
+        raise SystemExit("--dump-outputs writes the headline perft's outputs: the perft leg is not selected")
     # ------------------------------------------------- perft (headline: depth 7)
     p6 = p8 = p9 = None
     leaves, dt, ks = 0, 0.0, None
@@ -1037,8 +1069,12 @@ def main():
 
     if "perft" in legs:
         note("perft")
-        leaves, dt = timed_perft(eng, d, args, pos, args.depth, args.steps, args.warmup)
-        ks = profiled_perft(eng, d, args, pos, args.depth, args.steps)
+        kept = {}
+        leaves, dt = timed_perft(eng, d, args, pos, args.depth, args.steps, args.warmup, keep=kept)
+        if args.dump_outputs and d.rank == 0:
+            dump_outputs(args.dump_outputs, kept["last"])
+        if full:
+            ks = profiled_perft(eng, d, args, pos, args.depth, args.steps)
     # perft(6) (BASELINE configs[1]) on the same engine and method, secondary
     if "perft6" in legs:
         note("perft6")
@@ -1049,7 +1085,7 @@ def main():
     # one context (stream) per GPU: one run's latency, its front end not hidden
     # behind another run's final stage (the like-for-like figure)
     one = None
-    if "perft" in legs and (not args.profile_only or args.only):
+    if full and "perft" in legs and (not args.profile_only or args.only):
         note("perft_one_stream")
         one = {}
         for dd, k in ((args.depth, args.steps), (6, 4 * args.steps)):
@@ -1132,7 +1168,7 @@ def main():
         line["tx_signatures"] = txsig
     if v1 is not None:
         line["validate_n1_latency"] = v1
-    if not args.no_cpu and d.world == 1:
+    if full and not args.no_cpu and d.world == 1:
         threads = args.cpu_threads or host_cores()
         line.update(cpu_baselines(args, threads, replay_host))
         if txsig is not None:

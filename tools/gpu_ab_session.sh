@@ -21,11 +21,11 @@ if [ -n "${LIB_A:-}" ]; then
 fi
 if ! skip bench; then
   step bench
-  timeout -k 10 400 python -u bench.py > $O/bench_$T.json 2> $O/bench_$T.err || { tail -20 $O/bench_$T.err; exit 6; }
+  timeout -k 10 400 python -u bench.py --full > $O/bench_$T.json 2> $O/bench_$T.err || { tail -20 $O/bench_$T.err; exit 6; }
 fi
 if ! skip prof; then
   step prof
   rm -rf $O/prof_$T
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$T -o run --output-format csv -- python bench.py --no-cpu > $O/bench_prof_$T.json 2> $O/prof_$T.err || { tail -20 $O/prof_$T.err; exit 7; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$T -o run --output-format csv -- python bench.py --full --no-cpu > $O/bench_prof_$T.json 2> $O/prof_$T.err || { tail -20 $O/prof_$T.err; exit 7; }
 fi
 step done

@@ -19,13 +19,13 @@ if has test; then
 fi
 if has bench; then
   step bench
-  timeout -k 10 400 python -u bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 2; }
+  timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 2; }
   cat $O/bench.json
 fi
 if has prof; then
   step prof
   rm -rf $O/prof
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --no-cpu ${BENCH_ARGS} > $O/bench_prof.json 2> $O/prof.err || { tail -20 $O/prof.err; exit 3; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --full --no-cpu ${BENCH_ARGS} > $O/bench_prof.json 2> $O/prof.err || { tail -20 $O/prof.err; exit 3; }
 fi
 if has balance; then
   step balance
