@@ -26,6 +26,7 @@
 #include "dc_hash.h"
 #include "dc_keccak.h"
 #include "dc_kernels.h"
+#include "dc_movegen.h"
 #include "dc_perft.h"
 #include "dc_txsig_k.h"
 
@@ -109,6 +110,20 @@ struct HostIo {
 };
 constexpr uint32_t kHostFlagBatch = 256;
 
+// dc_legal_moves_batch of at most one block (the one-position call of a front
+// end): positions in, offsets / status / total / moves out, all in one pinned
+// block the fused kernel reads and writes in place.  A batch whose moves do
+// not fit kLegalIoMoves takes the three-launch path through device buffers.
+constexpr uint32_t kLegalIoMoves = 256 * 256;
+struct LegalIo {
+  dc_pos pos[dc::kLegalBlock];
+  uint32_t offsets[dc::kLegalBlock + 1];
+  uint8_t status[dc::kLegalBlock];
+  uint64_t total;  // also the three-launch path's total (k_legal_scan stores it here)
+  uint32_t done;
+  alignas(16) uint16_t moves[kLegalIoMoves];
+};
+
 struct dc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -138,7 +153,8 @@ struct dc_ctx {
   u32* plain_host = nullptr;             // pinned: the state hash's names check (k_names_plain's flag)
   hipEvent_t plain_ev = nullptr;         // ... recorded after its readback
   struct HostIo* host_io = nullptr;      // pinned: small validate / apply batches, read and written in place
-  uint32_t io_seq = 0;                   // last completion flag value published into host_io->done
+  uint32_t io_seq = 0;                   // last completion flag value published into host_io->done / legal_io->done
+  struct LegalIo* legal_io = nullptr;    // pinned: dc_legal_moves_batch* (small batches in place; the total)
   // dc_live_validator: the resident wave's mailbox (pinned, coherent), its
   // stream, the requests it has served and its lease (0: off)
   dc::LiveBox* live = nullptr;
@@ -188,6 +204,10 @@ struct dc_ctx {
   DBuf<DevPos> pos;
   DBuf<uint16_t> moves;
   DBuf<uint8_t> verdicts, info;
+  // dc_legal_moves_batch*: block sums and bases; the host form's device-side outputs
+  DBuf<u32> legal_bsum, legal_bbase, legal_off;
+  DBuf<uint8_t> legal_status;
+  DBuf<uint16_t> legal_moves;
   DBuf<uint8_t> replay_info;  // dc_replay_info / the state hash's first pass: ply-major [n_plies][n_games] move info
   DBuf<Board> hash_boards;    // the state hash's first pass: every game's final board (round 6)
   DBuf<char> hash_text;    // escaped start history | escaped names of dc_state_hash*
@@ -257,10 +277,16 @@ struct dc_ctx {
     if (plain_host) (void)hipHostFree(plain_host);
     if (plain_ev) (void)hipEventDestroy(plain_ev);
     if (host_io) (void)hipHostFree(host_io);
+    if (legal_io) (void)hipHostFree(legal_io);
     if (live) (void)hipHostFree(live);
     if (live_stream) (void)hipStreamDestroy(live_stream);
     if (root_host) (void)hipHostFree(root_host);
     pos.release();
+    legal_bsum.release();
+    legal_bbase.release();
+    legal_off.release();
+    legal_status.release();
+    legal_moves.release();
     verdicts.release();
     info.release();
     replay_info.release();
@@ -914,6 +940,163 @@ int dc_apply_batch(dc_ctx* c, uint32_t rules, dc_pos* pos, const uint16_t* moves
   HIP_TRY(hipMemcpyAsync(verdicts, c->verdicts.p, n, hipMemcpyDeviceToHost, c->stream));
   if (info) HIP_TRY(hipMemcpyAsync(info, c->info.p, n, hipMemcpyDeviceToHost, c->stream));
   return sync_ctx(c);
+}
+
+// ============================================================= legal moves
+static bool legal_plain() {
+  const char* e = dc::ab_env("DC_LEGAL_EMIT");  // A/B build only
+  return e && std::strcmp(e, "plain") == 0;
+}
+
+static int legal_io_ensure(dc_ctx* c) {
+  if (c->legal_io) return DC_SUCCESS;
+  HIP_TRY(hipHostMalloc((void**)&c->legal_io, sizeof(LegalIo), hipHostMallocCoherent));
+  c->legal_io->done = 0;  // io_seq's values start at 1
+  c->legal_io->total = 0;
+  return DC_SUCCESS;
+}
+
+// n <= kLegalBlock: the fused kernel on the given buffers (device memory, or
+// the pinned LegalIo); the total comes back through legal_io->total.
+static int legal_small(dc_ctx* c, uint32_t rules, const DevPos* pos, uint32_t n, u32* offsets, uint8_t* status,
+                       uint16_t* moves, uint32_t cap, u64* total) {
+  LegalIo* h = c->legal_io;
+  const bool flag = !c->profiling;
+  const uint32_t seq = flag ? next_seq(c) : 0u;
+  uint32_t* done = flag ? &h->done : nullptr;
+  HIP_TRY(c->timed("legal_small", n, [&] {
+    return dc::launch_legal_small(c->stream, rules, pos, n, offsets, status, moves, cap,
+                                  reinterpret_cast<u64*>(&h->total), done, seq, legal_plain());
+  }));
+  const int e = flag ? wait_host_flag(c, done, seq) : sync_ctx(c);
+  if (e != DC_SUCCESS) return e;
+  *total = __atomic_load_n(&h->total, __ATOMIC_ACQUIRE);
+  return DC_SUCCESS;
+}
+
+// Any n, device buffers: counts, status and block-local offsets, then the scan
+// of the block sums; returns with the 64-bit total on the host.
+static int legal_count_scan(dc_ctx* c, uint32_t rules, const DevPos* d_pos, uint32_t n, u32* d_offsets,
+                            uint8_t* d_status, u64* total) {
+  const u32 nb = (n + dc::kLegalBlock - 1) / dc::kLegalBlock;
+  HIP_TRY(c->legal_bsum.ensure(nb));
+  HIP_TRY(c->legal_bbase.ensure(nb));
+  HIP_TRY(c->timed("legal_count", n, [&] {
+    return dc::launch_legal_count(c->stream, rules, d_pos, n, d_offsets, d_status, c->legal_bsum.p);
+  }));
+  HIP_TRY(c->timed("legal_scan", nb, [&] {
+    return dc::launch_legal_scan(c->stream, c->legal_bsum.p, nb, c->legal_bbase.p, d_offsets + n,
+                                 reinterpret_cast<u64*>(&c->legal_io->total));
+  }));
+  const int e = sync_ctx(c);
+  if (e != DC_SUCCESS) return e;
+  *total = __atomic_load_n(&c->legal_io->total, __ATOMIC_ACQUIRE);
+  return DC_SUCCESS;
+}
+
+// The second half: the moves (d_moves != nullptr: `total` of them fit) with the
+// final offsets, or the final offsets alone.  Enqueued, not synchronised.
+static int legal_finish(dc_ctx* c, uint32_t rules, const DevPos* d_pos, uint32_t n, u32* d_offsets,
+                        uint16_t* d_moves, uint32_t total) {
+  if (d_moves) {
+    HIP_TRY(c->timed("legal_emit", total, [&] {
+      return dc::launch_legal_emit(c->stream, rules, d_pos, n, d_offsets, c->legal_bsum.p, c->legal_bbase.p, d_moves,
+                                   total, legal_plain());
+    }));
+  } else {
+    HIP_TRY(c->timed("legal_fixup", n, [&] {
+      return dc::launch_legal_fixup(c->stream, d_offsets, n, c->legal_bbase.p);
+    }));
+  }
+  return DC_SUCCESS;
+}
+
+int dc_legal_moves_batch_device(dc_ctx* c, uint32_t rules, const dc_pos* d_pos, uint32_t n, uint32_t* d_offsets,
+                                uint8_t* d_status, uint16_t* d_moves, uint32_t moves_cap, uint32_t* total) {
+  ENTER_WORK(c);
+  if (rules > DC_RULES_FIDE || (n && (!d_pos || !d_offsets))) return DC_EINVAL;
+  if (total) *total = 0;
+  if (n == 0) {
+    if (d_offsets) {
+      HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
+      return sync_ctx(c);
+    }
+    return DC_SUCCESS;
+  }
+  int e = legal_io_ensure(c);
+  if (e != DC_SUCCESS) return e;
+  const bool sizing = !d_moves || moves_cap == 0;
+  const DevPos* dp = reinterpret_cast<const DevPos*>(d_pos);
+  u64 t = 0;
+  if (n <= dc::kLegalBlock) {
+    e = legal_small(c, rules, dp, n, d_offsets, d_status, sizing ? nullptr : d_moves, sizing ? 0u : moves_cap, &t);
+    if (e != DC_SUCCESS) return e;
+    if (total) *total = (uint32_t)t;
+    return (!sizing && t > moves_cap) ? DC_EINVAL : DC_SUCCESS;
+  }
+  e = legal_count_scan(c, rules, dp, n, d_offsets, d_status, &t);
+  if (e != DC_SUCCESS) return e;
+  if (t > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+  if (total) *total = (uint32_t)t;
+  const bool fill = !sizing && t <= moves_cap;
+  e = legal_finish(c, rules, dp, n, d_offsets, fill ? d_moves : nullptr, (uint32_t)t);
+  if (e != DC_SUCCESS) return e;
+  e = sync_ctx(c);
+  if (e != DC_SUCCESS) return e;
+  return (sizing || fill) ? DC_SUCCESS : DC_EINVAL;
+}
+
+int dc_legal_moves_batch(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t n, uint32_t* offsets, uint8_t* status,
+                         uint16_t* moves, uint32_t moves_cap, uint32_t* total) {
+  ENTER_WORK(c);
+  if (rules > DC_RULES_FIDE || (n && (!pos || !offsets))) return DC_EINVAL;
+  if (total) *total = 0;
+  if (n == 0) {
+    if (offsets) offsets[0] = 0;
+    return DC_SUCCESS;
+  }
+  int e = legal_io_ensure(c);
+  if (e != DC_SUCCESS) return e;
+  const bool sizing = !moves || moves_cap == 0;
+  u64 t = 0;
+  if (n <= dc::kLegalBlock) {  // pinned, read and written in place by the kernel
+    LegalIo* h = c->legal_io;
+    std::memcpy(h->pos, pos, sizeof(dc_pos) * n);
+    const uint32_t kcap = sizing ? 0u : std::min(moves_cap, kLegalIoMoves);
+    e = legal_small(c, rules, reinterpret_cast<const DevPos*>(h->pos), n, h->offsets, h->status,
+                    sizing ? nullptr : h->moves, kcap, &t);
+    if (e != DC_SUCCESS) return e;
+    std::memcpy(offsets, h->offsets, sizeof(uint32_t) * ((size_t)n + 1));
+    if (status) std::memcpy(status, h->status, n);
+    if (total) *total = (uint32_t)t;
+    if (sizing) return DC_SUCCESS;
+    if (t > moves_cap) return DC_EINVAL;
+    if (t <= kcap) {
+      std::memcpy(moves, h->moves, sizeof(uint16_t) * (size_t)t);
+      return DC_SUCCESS;
+    }
+    // more moves than the pinned block holds: the three-launch path
+  }
+  HIP_TRY(c->pos.ensure(n));
+  HIP_TRY(c->legal_off.ensure((size_t)n + 1));
+  HIP_TRY(c->legal_status.ensure(n));
+  HIP_TRY(hipMemcpyAsync(c->pos.p, pos, sizeof(dc_pos) * n, hipMemcpyHostToDevice, c->stream));
+  e = legal_count_scan(c, rules, c->pos.p, n, c->legal_off.p, c->legal_status.p, &t);
+  if (e != DC_SUCCESS) return e;
+  if (t > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+  if (total) *total = (uint32_t)t;
+  const bool fill = !sizing && t <= moves_cap;
+  if (fill) HIP_TRY(c->legal_moves.ensure(std::max<size_t>((size_t)t, 1)));
+  e = legal_finish(c, rules, c->pos.p, n, c->legal_off.p, fill ? c->legal_moves.p : nullptr, (uint32_t)t);
+  if (e != DC_SUCCESS) return e;
+  HIP_TRY(hipMemcpyAsync(offsets, c->legal_off.p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost,
+                         c->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(status, c->legal_status.p, n, hipMemcpyDeviceToHost, c->stream));
+  if (fill && t)
+    HIP_TRY(hipMemcpyAsync(moves, c->legal_moves.p, sizeof(uint16_t) * (size_t)t, hipMemcpyDeviceToHost, c->stream));
+  e = sync_ctx(c);
+  if (e != DC_SUCCESS) return e;
+  return (sizing || fill) ? DC_SUCCESS : DC_EINVAL;
 }
 
 // ================================================================== replay

@@ -22,6 +22,7 @@ SUCCESS, EINVAL, EHIP, ENOMEM, ENODEV, ERCCL, EUNSUPPORTED = 0, -1, -2, -3, -4, 
 V_OK, V_NO_PIECE, V_WRONG_TURN, V_ILLEGAL, V_OOR = 0, 1, 2, 3, 4
 RULES_REF, RULES_FIDE = 0, 1
 MOVE_OOR, MOVE_NONE = 0x8000, 0xFFFF
+ST_CHECK, ST_NO_MOVES, ST_DEAD = 1, 2, 4  # dc_legal_moves_batch status bits
 CELL_EMPTY = -1
 KINDS = "PNBRQKX"  # cell kind order of the ABI (X = unknown kind string)
 
@@ -81,7 +82,11 @@ def lib():
         "dc_validate_batch": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
         "dc_apply_batch": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
         "dc_live_validator": (C.c_int, [_vp, C.c_uint32]),
-        "dc_replay": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_Stats)]),
+        "dc_legal_moves_batch": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32,
+                                           C.POINTER(C.c_uint32)]),
+        "dc_legal_moves_batch_device": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32,
+                                                  C.POINTER(C.c_uint32)]),
+        "dc_replay":(C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_Stats)]),
         "dc_replay_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp,
                                        C.POINTER(_Stats)]),
         "dc_replay_info": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
@@ -381,6 +386,33 @@ class Engine:
                "dc_apply_batch")
         return pos, ver, info
 
+    # --------------------------------------------------------- legal moves
+    def legal_moves(self, pos, rules=RULES_REF):
+        """dc_legal_moves_batch: a sizing call, then a fill call.  Returns
+        (offsets u32[n+1], moves u16[total], status u8[n]): position i's legal
+        moves are moves[offsets[i]:offsets[i+1]] in (from, to, promo) order."""
+        pos = np.ascontiguousarray(pos, POS_DTYPE).reshape(-1)
+        n = len(pos)
+        off = np.zeros(n + 1, np.uint32)
+        st = np.zeros(n, np.uint8)
+        tot = C.c_uint32()
+        _check(lib().dc_legal_moves_batch(self.ctx, rules, _ptr(pos), n, _ptr(off), _ptr(st), None, 0,
+                                          C.byref(tot)), "dc_legal_moves_batch")
+        mv = np.zeros(tot.value, np.uint16)
+        if tot.value:
+            _check(lib().dc_legal_moves_batch(self.ctx, rules, _ptr(pos), n, _ptr(off), _ptr(st), _ptr(mv),
+                                              tot.value, C.byref(tot)), "dc_legal_moves_batch")
+        return off, mv, st
+
+    def legal_moves_device(self, d_pos, n, d_offsets, d_status, d_moves, moves_cap, rules=RULES_REF):
+        """dc_legal_moves_batch_device on DeviceBuffers or raw device addresses
+        (d_status / d_moves may be None).  Returns the total number of moves."""
+        tot = C.c_uint32()
+        _check(lib().dc_legal_moves_batch_device(self.ctx, rules, _dptr(d_pos), n, _dptr(d_offsets),
+                                                 _dptr(d_status), _dptr(d_moves), moves_cap, C.byref(tot)),
+               "dc_legal_moves_batch_device")
+        return int(tot.value)
+
     # -------------------------------------------------------------- replay
     def replay(self, moves, rules=RULES_REF, start=None, want_bitmap=True, want_digests=True):
         """moves: uint16 [n_plies, n_games] ply-major.  Returns (bitmap, digests, stats dict)."""
@@ -651,6 +683,13 @@ class GameState:
             raise IndexError("index out of bounds")  # the reference panics here
         if v != V_OK:
             raise AppError(verdict_message(v))
+
+    def legal_moves(self):
+        """Every (from, to) Position pair validate_move accepts on this board
+        and turn, in (from, to) order (dc_legal_moves_batch, n = 1)."""
+        _, mv, _ = self.engine.legal_moves(np.array([self._pos()], POS_DTYPE))
+        return [(Position((m & 63) >> 3, m & 7), Position(((m >> 6) & 63) >> 3, (m >> 6) & 7))
+                for m in mv.tolist()]
 
     def apply_move(self, frm, to):  # chess.rs:43-80
         pos = np.array([self._pos()], POS_DTYPE)

@@ -128,7 +128,9 @@ const char* dc_verdict_message(uint8_t verdict);
 int dc_version(void);
 
 /* Per-kernel HIP-event timing (enable, read, reset).  Kernel names:
- * "validate", "replay", "gen_games", "expand_count", "expand_write", "count1", "count2". */
+ * "validate", "replay", "gen_games", "expand_count", "expand_write", "count1", "count2",
+ * "legal_count" (units: positions), "legal_emit" (units: moves); beside them
+ * "legal_scan", "legal_fixup" and, for batches of at most 256, "legal_small". */
 int dc_ctx_set_profiling(dc_ctx* ctx, int enable);
 int dc_ctx_kernel_stats(dc_ctx* ctx, const char* kernel, dc_kernel_stats* out);
 int dc_ctx_reset_stats(dc_ctx* ctx);
@@ -165,6 +167,34 @@ int dc_validate_batch(dc_ctx* ctx, uint32_t rules, const dc_pos* pos, const uint
  * which is what update_history needs (chess.rs:156-167). */
 int dc_apply_batch(dc_ctx* ctx, uint32_t rules, dc_pos* pos, const uint16_t* moves, uint32_t n,
                    uint8_t* verdicts, uint8_t* info);
+
+/* ------------------------------------------------------------ legal moves
+ * The legal moves and the game status of n positions, as a dense CSR:
+ * offsets (required, n + 1 entries) is the exclusive prefix sum of the
+ * positions' move counts (offsets[0] = 0, *total = offsets[n]; no gaps, no
+ * per-position cap), and moves[offsets[i] .. offsets[i+1]) are pos[i]'s moves
+ * as move words in (from, to, promo) order: from ascending, then to, then
+ * promo N, B, R, Q -- the order of dc_gen_games' k-th legal move (dc_perft's
+ * root_moves are the same moves in its generator's order).  Under DC_RULES_REF the
+ * list is every (from, to) dc_validate_batch accepts, under DC_RULES_FIDE
+ * every (from, to, promo) (positions with at most one king per side, as
+ * everywhere under FIDE).  stm is taken as stm & 1; castle and ep are ignored
+ * under REF.
+ * status (optional, n entries) holds DC_ST_* bits; total is optional.
+ * moves == NULL or moves_cap == 0 only sizes: offsets, status and total are
+ * written, DC_SUCCESS.  0 < moves_cap < total writes offsets, status and
+ * total, nothing into moves, and returns DC_EINVAL; nothing is ever written
+ * at or past moves[moves_cap].  A total of 2^32 or more is DC_EUNSUPPORTED.
+ * The _device form takes device pointers (total stays a host pointer) and
+ * returns once the results are complete. */
+#define DC_ST_CHECK 1u    /* FIDE: the side to move's king is attacked */
+#define DC_ST_NO_MOVES 2u /* no legal move (FIDE: CHECK|NO_MOVES = checkmate, NO_MOVES alone = stalemate) */
+#define DC_ST_DEAD 4u     /* FIDE: insufficient material -- only kings, knights and bishops, and at most
+                             one knight or bishop in all, or no knight and all bishops on one square colour */
+int dc_legal_moves_batch(dc_ctx* ctx, uint32_t rules, const dc_pos* pos, uint32_t n, uint32_t* offsets,
+                         uint8_t* status, uint16_t* moves, uint32_t moves_cap, uint32_t* total);
+int dc_legal_moves_batch_device(dc_ctx* ctx, uint32_t rules, const dc_pos* d_pos, uint32_t n, uint32_t* d_offsets,
+                                uint8_t* d_status, uint16_t* d_moves, uint32_t moves_cap, uint32_t* total);
 
 /* The live validator (opt-in, per context): with lease_us > 0, every
  * dc_validate_batch / dc_apply_batch call of at most 64 moves on this context

@@ -63,6 +63,9 @@ pub mod sys {
     pub const DC_MOVE_OOR: u16 = 0x8000;
     pub const DC_MOVE_NONE: u16 = 0xFFFF;
     pub const DC_CELL_EMPTY: i8 = -1;
+    pub const DC_ST_CHECK: u8 = 1;
+    pub const DC_ST_NO_MOVES: u8 = 2;
+    pub const DC_ST_DEAD: u8 = 4;
     pub const DC_SIG_OK: u8 = 0;
     pub const DC_SIG_BAD_SIG_HEX: u8 = 1;
     pub const DC_SIG_BAD_SIG: u8 = 2;
@@ -100,6 +103,12 @@ pub mod sys {
         pub fn dc_apply_batch(ctx: *mut dc_ctx, rules: u32, pos: *mut dc_pos, moves: *const u16, n: u32,
                               verdicts: *mut u8, info: *mut u8) -> c_int;
         pub fn dc_live_validator(ctx: *mut dc_ctx, lease_us: u32) -> c_int;
+        // legal moves
+        pub fn dc_legal_moves_batch(ctx: *mut dc_ctx, rules: u32, pos: *const dc_pos, n: u32, offsets: *mut u32,
+                                    status: *mut u8, moves: *mut u16, moves_cap: u32, total: *mut u32) -> c_int;
+        pub fn dc_legal_moves_batch_device(ctx: *mut dc_ctx, rules: u32, d_pos: *const dc_pos, n: u32,
+                                           d_offsets: *mut u32, d_status: *mut u8, d_moves: *mut u16,
+                                           moves_cap: u32, total: *mut u32) -> c_int;
         // replay
         pub fn dc_replay(ctx: *mut dc_ctx, rules: u32, start: *const dc_pos, moves: *const u16, n_games: u32,
                          n_plies: u32, bitmap: *mut u64, digests: *mut u64, stats: *mut dc_replay_stats) -> c_int;
@@ -249,6 +258,27 @@ impl Engine {
         check(unsafe { sys::dc_validate_batch(self.0, sys::DC_RULES_REF, pos.as_ptr(), moves.as_ptr(),
                                               pos.len() as u32, v.as_mut_ptr()) }, "dc_validate_batch")?;
         Ok(v.into_iter().map(verdict).collect())
+    }
+
+    /// The legal moves and DC_ST_* status of every position (dc_legal_moves_batch):
+    /// a sizing call, then a fill call.  Returns (offsets [n + 1], moves [total],
+    /// status [n]); position i's moves are moves[offsets[i] .. offsets[i + 1]).
+    pub fn legal_moves(&self, rules: u32, pos: &[sys::dc_pos]) -> Result<(Vec<u32>, Vec<u16>, Vec<u8>), DcError> {
+        let n = u32::try_from(pos.len()).map_err(|_| DcError {
+            status: sys::DC_EINVAL, what: "dc_legal_moves_batch", text: "more than u32::MAX positions".into() })?;
+        let mut offsets = vec![0u32; pos.len() + 1];
+        let mut status = vec![0u8; pos.len()];
+        let mut total = 0u32;
+        check(unsafe { sys::dc_legal_moves_batch(self.0, rules, pos.as_ptr(), n, offsets.as_mut_ptr(),
+                                                 status.as_mut_ptr(), std::ptr::null_mut(), 0, &mut total) },
+              "dc_legal_moves_batch")?;
+        let mut moves = vec![0u16; total as usize];
+        if total != 0 {
+            check(unsafe { sys::dc_legal_moves_batch(self.0, rules, pos.as_ptr(), n, offsets.as_mut_ptr(),
+                                                     status.as_mut_ptr(), moves.as_mut_ptr(), total, &mut total) },
+                  "dc_legal_moves_batch")?;
+        }
+        Ok((offsets, moves, status))
     }
 
     /// apply_move (chess.rs:43-80) on the cells of a proto board: validates,
