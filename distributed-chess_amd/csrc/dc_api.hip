@@ -1357,9 +1357,6 @@ int state_hash_impl(dc_ctx* c, const dc_pos* start, const char* history, const c
     const int e = begin_names_check(c, d_names, d_names_off, n_games);
     if (e != DC_SUCCESS) return e;
   }
-#ifndef DC_HASH_PRE
-#define DC_HASH_PRE 1  // (0: the round-4 single kernel, for A/B only)
-#endif
   // The pre-pass is an optimisation: when its buffers (up to ~2 GiB near the
   // move bound) cannot be had, or exceed the context's pre-pass budget (a test
   // hook), the hash kernel validates on its own instead of the call failing.
@@ -1367,8 +1364,7 @@ int state_hash_impl(dc_ctx* c, const dc_pos* start, const char* history, const c
   // so the hash kernel makes no move)
   const u64 pre_bytes = (u64)n_games * n_plies + 8 * (5 + 5 * (u64)dc::replay_partials(n_games)) +
                         sizeof(Board) * (u64)n_games;
-  bool pre = DC_HASH_PRE && n_plies > 0 && (u64)n_games * n_plies * 2 <= 0xFFFFFFFFull &&
-             pre_bytes <= c->hash_prepass_max;
+  bool pre = n_plies > 0 && (u64)n_games * n_plies * 2 <= 0xFFFFFFFFull && pre_bytes <= c->hash_prepass_max;
   if (pre && (c->replay_info.ensure((size_t)n_games * n_plies) != hipSuccess ||
               c->hash_boards.ensure(n_games) != hipSuccess ||
               c->stats5.ensure(5 + 5 * (size_t)dc::replay_partials(n_games)) != hipSuccess)) {

@@ -31,54 +31,22 @@ constexpr u64 kDiagAnti = 0x0102040810204080ull;  // h1..a8 (x + y == 7)
 // so one 64-bit shift (4 cycles per wave) beats the compiler's habit of
 // splitting it into v_alignbit_b32 + v_lshlrev_b32 once the halves feed
 // 32-bit bitop3s (tools/ubench/vop_rate.hip, profiles/r01/ubench_vop.txt).
-// DC_SHIFT_PAD selects how the shift is written: 0 (shipped) the inline-asm
-// shift; A/B diagnostics only: 4 = an opaque SGPR shift amount (shift_amount;
-// measured slower in round 4), 1 = s_nop 1 ahead of the asm shift, 2 = s_nop 1
-// after it, 3 = plain C shifts.
-#ifndef DC_SHIFT_PAD
-#define DC_SHIFT_PAD 0
-#endif
-#if DC_SHIFT_PAD == 1
-#define DC_SHL_ASM "s_nop 1\n\tv_lshlrev_b64 %0, %1, %2"
-#define DC_SHR_ASM "s_nop 1\n\tv_lshrrev_b64 %0, %1, %2"
-#elif DC_SHIFT_PAD == 2
-#define DC_SHL_ASM "v_lshlrev_b64 %0, %1, %2\n\ts_nop 1"
-#define DC_SHR_ASM "v_lshrrev_b64 %0, %1, %2\n\ts_nop 1"
-#else
-#define DC_SHL_ASM "v_lshlrev_b64 %0, %1, %2"
-#define DC_SHR_ASM "v_lshrrev_b64 %0, %1, %2"
-#endif
-// The shift amount as an opaque SGPR constant (DC_SHIFT_PAD == 4, round 4):
-// the compiler cannot split a shift by an unknown amount into 32-bit halves,
-// so it emits the one v_lshlrev_b64 itself -- and, unlike after an inline-asm
-// shift, it knows that instruction's hazards, so no conservative s_nop 0
-// follows each shift (15M s_nop per perft(7) launch of k_count3c,
-// tools/bbprof.py).
-template <int A>
-__device__ __forceinline__ u32 shift_amount() {
-  u32 k;
-  asm("s_mov_b32 %0, %1" : "=s"(k) : "i"(A));
-  return k;
-}
+// History (round 4, the retired DC_SHIFT_PAD switch): four other spellings
+// were measured against the inline-asm shift and lost -- an s_nop 1 ahead of
+// or after the asm shift, plain C shifts, and the shift amount as an opaque
+// SGPR constant.  The last makes the compiler emit the one v_lshlrev_b64
+// itself without the conservative s_nop 0 it puts after an inline-asm shift
+// (15M s_nop per perft(7) launch of k_count3c, tools/bbprof.py), yet measured
+// slower.
 template <int S>
 __device__ __forceinline__ u64 sh(u64 x) {
   u64 r;
-#if DC_SHIFT_PAD == 4
-  if constexpr (S >= 32) r = (u64)((u32)x << (S - 32)) << 32;
-  else if constexpr (S <= -32) r = (u64)((u32)(x >> 32) >> (-S - 32));
-  else if constexpr (S > 0) r = x << shift_amount<S>();
-  else if constexpr (S < 0) r = x >> shift_amount<-S>();
-#elif DC_SHIFT_PAD == 3
-  if constexpr (S > 0) r = x << S;
-  else if constexpr (S < 0) r = x >> -S;
-#else
   // |S| >= 32 (the fills' 4 x 8 and 4 x 9 steps): one half moves, so a 32-bit
   // shift (S = 32: a register copy) instead of the half-rate 64-bit one
   if constexpr (S >= 32) r = (u64)((u32)x << (S - 32)) << 32;
   else if constexpr (S <= -32) r = (u64)((u32)(x >> 32) >> (-S - 32));
-  else if constexpr (S > 0) asm(DC_SHL_ASM : "=v"(r) : "i"(S), "v"(x));
-  else if constexpr (S < 0) asm(DC_SHR_ASM : "=v"(r) : "i"(-S), "v"(x));
-#endif
+  else if constexpr (S > 0) asm("v_lshlrev_b64 %0, %1, %2" : "=v"(r) : "i"(S), "v"(x));
+  else if constexpr (S < 0) asm("v_lshrrev_b64 %0, %1, %2" : "=v"(r) : "i"(-S), "v"(x));
   else r = x;
   return r;
 }
@@ -131,11 +99,9 @@ __device__ __forceinline__ u64 ray_moves(u64 gen, u64 empty, u64 allowed) {
 // in each CU's vector L1): one vector load replaces a variable 64-bit shift
 // pair, its select and the wrap-file select.  Round 4 (tools/bbprof_inline.py
 // on k_count3c): king_moves was 5.6 % of the kernel's VALU issue cycles and
-// slider_source ~7 %, almost all of it that arithmetic.  DC_ATT_TAB=0 keeps
-// the arithmetic forms (A/B).
-#ifndef DC_ATT_TAB
-#define DC_ATT_TAB 1
-#endif
+// slider_source ~7 %, almost all of it that arithmetic; the arithmetic forms
+// lost that A/B (the retired DC_ATT_TAB switch) and are gone except where a
+// caller asks for one (line_behind<D, false>).
 struct AttTables {
   u64 king[64], knight[64];
   u64 behind[8][64];  // line_behind<D>(t)
@@ -165,7 +131,7 @@ __constant__ constexpr AttTables kAtt{};
 // TAB false: the arithmetic form (the FIDE generator's single-workgroup top
 // plies are latency-bound, and a table load sits on their dependency chain:
 // FIDE suite at depth 5 2.65 -> 2.79 ms with the table, round 4 A/B)
-template <int D, bool TAB = (DC_ATT_TAB != 0)>
+template <int D, bool TAB = true>
 __device__ __forceinline__ u64 line_behind(int t) {
   if constexpr (TAB) return kAtt.behind[D][t];
   const int x = t >> 3, y = t & 7;
@@ -187,7 +153,7 @@ __device__ __forceinline__ u64 line_behind(int t) {
 
 // Source square of a slider move toward D that lands on t: the nearest
 // occupied square behind t.
-template <int D, bool TAB = (DC_ATT_TAB != 0)>
+template <int D, bool TAB = true>
 __device__ __forceinline__ int slider_source(u64 occ, int t) {
   const u64 c = occ & line_behind<D, TAB>(t);
   if constexpr ((D & 1) == 0) return msb(c);

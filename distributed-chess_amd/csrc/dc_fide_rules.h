@@ -35,52 +35,12 @@ __device__ __forceinline__ u64 king_attacks(u64 k) {
   return sh<8>(k) | sh<-8>(k) | sh<1>(k & kNotH) | sh<-1>(k & kNotA) | sh<9>(k & kNotH) | sh<7>(k & kNotA) |
          sh<-7>(k & kNotH) | sh<-9>(k & kNotA);
 }
-// TAB: king and knight attack sets from kAtt (one L1 load per piece instead
-// of eight shifts) -- the final stage's leaf counts only (k_count2b); the
-// single-workgroup top plies are latency-bound and keep the shifts
-#ifndef DC_FIDE_TAB_UNCOND
-#define DC_FIDE_TAB_UNCOND 0
-#endif
-#ifndef DC_FIDE_TAB_PARTS
-#define DC_FIDE_TAB_PARTS 7  // (diagnostics) 1 king sets, 2 enemy knight sets, 4 own knight counts
-#endif
-template <bool TAB>
-__device__ __forceinline__ u64 king_attacks_t(u64 k) {
-  if constexpr (TAB && (DC_FIDE_TAB_PARTS & 1)) {
-#if DC_FIDE_TAB_UNCOND == 1
-    // (diagnostics) the load issued by every lane, outside the branch
-    u64 t = kAtt.king[lsb(k | (1ull << 63)) & 63];
-    asm volatile("" : "+v"(t));
-    if ((k & (k - 1)) == 0) return k ? t : 0ull;
-#elif DC_FIDE_TAB_UNCOND == 2
-    // (diagnostics) the load waited for at once
-    if ((k & (k - 1)) == 0) {
-      u64 t = k ? kAtt.king[lsb(k) & 63] : 0ull;
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(t)::"memory");
-      return t;
-    }
-#elif DC_FIDE_TAB_UNCOND == 3
-    // (diagnostics) the table address in VGPRs (no SGPR base operand)
-    if ((k & (k - 1)) == 0) {
-      const u64* base = &kAtt.king[0];
-      asm volatile("" : "+v"(base));
-      return k ? base[lsb(k) & 63] : 0ull;
-    }
-#else
-    if ((k & (k - 1)) == 0) return k ? kAtt.king[lsb(k) & 63] : 0ull;
-#endif
-  }
-  return king_attacks(k);
-}
-template <bool TAB>
-__device__ __forceinline__ u64 knight_attacks_t(u64 n) {
-  if constexpr (TAB && (DC_FIDE_TAB_PARTS & 2)) {
-    u64 a = 0;
-    for (; n; n &= n - 1) a |= kAtt.knight[lsb(n) & 63];
-    return a;
-  }
-  return knight_attacks(n);
-}
+// Round 4 tried king and knight attack sets from kAtt here (one L1 load per
+// piece instead of eight shifts) for the final stage's leaf counts, behind a
+// TAB template parameter of fide_count / analyse.  That variant miscounted in
+// round 4 (the exposed gate window of DESIGN.md §3.6, see analyse), never
+// shipped and is gone.  The single-workgroup top plies are latency-bound and
+// want the shifts anyway.
 __device__ __forceinline__ u64 orth_attacks(u64 s, u64 empty) {
   return ray_attacks<8, kAll>(s, empty) | ray_attacks<-8, kAll>(s, empty) | ray_attacks<1, kNotA>(s, empty) |
          ray_attacks<-1, kNotH>(s, empty);
@@ -186,25 +146,17 @@ __device__ __forceinline__ void scan_dir(const FPos<STM>& f, u64 kup, u64 kdn, c
   pinned |= ((m2 & sl) ? (m1 & f.us) : 0ull);
 }
 
-#ifndef DC_FIDE_SNIPER
-#define DC_FIDE_SNIPER 1
-#endif
-#ifndef DC_FIDE_LAZY_DANGER
-#define DC_FIDE_LAZY_DANGER 0  // 1: fide_count computes the attack map only in waves that need it (2: also
-                               // the split's passes) -- measured slower, off
-#endif
-// with_danger = false (wave-uniform): no attack map; danger reads "every
-// square attacked", i.e. no king move and no castling -- for callers whose
-// lanes have neither a free square next to the king nor an open castling path
-template <int STM, bool TAB = false>
-__device__ __forceinline__ Analysis analyse(const FPos<STM>& f, bool with_danger = true) {
+// The attack map is computed for every position.  Skipping it (danger = "every
+// square attacked") in waves none of whose lanes has a free square next to
+// the king or an open castling path was measured slower and is
+// gone.
+template <int STM>
+__device__ __forceinline__ Analysis analyse(const FPos<STM>& f) {
   constexpr int THEM = 1 - STM;
   Analysis a;
   const u64 empty_nk = f.empty | f.K;
-  a.danger = ~0ull;
-  if (with_danger)
-    a.danger = pawn_attacks<THEM>(f.tP) | knight_attacks_t<TAB>(f.tN) | king_attacks_t<TAB>(f.tK) |
-               orth_attacks(f.tO, empty_nk) | diag_attacks(f.tD, empty_nk);
+  a.danger = pawn_attacks<THEM>(f.tP) | knight_attacks(f.tN) | king_attacks(f.tK) | orth_attacks(f.tO, empty_nk) |
+             diag_attacks(f.tD, empty_nk);
   a.checkers = 0;
   a.pinned = 0;
   a.ksq = f.K ? lsb(f.K) : -1;
@@ -221,25 +173,6 @@ __device__ __forceinline__ Analysis analyse(const FPos<STM>& f, bool with_danger
   u64 kup = above_mask(a.ksq), kdn = below_mask(a.ksq);
   asm volatile("" : "+v"(kup), "+v"(kdn));
   u64 chk = a.checkers, pin = 0;
-#if DC_FIDE_SNIPER == 2
-  // (diagnostics) the same gate as a per-lane branch (no __ballot)
-  if ((l.file & f.tO) != 0) {
-    scan_dir<STM, 0>(f, kup, kdn, l, chk, pin);
-    scan_dir<STM, 1>(f, kup, kdn, l, chk, pin);
-  }
-  if ((l.rank & f.tO) != 0) {
-    scan_dir<STM, 2>(f, kup, kdn, l, chk, pin);
-    scan_dir<STM, 3>(f, kup, kdn, l, chk, pin);
-  }
-  if ((l.diag & f.tD) != 0) {
-    scan_dir<STM, 4>(f, kup, kdn, l, chk, pin);
-    scan_dir<STM, 5>(f, kup, kdn, l, chk, pin);
-  }
-  if ((l.anti & f.tD) != 0) {
-    scan_dir<STM, 6>(f, kup, kdn, l, chk, pin);
-    scan_dir<STM, 7>(f, kup, kdn, l, chk, pin);
-  }
-#elif DC_FIDE_SNIPER
   // a line through the king with no enemy slider of its kind on it can hold
   // neither a slider check nor a pin: a wave none of whose lanes has one
   // skips that line's two scans (round 4: the eight scans were ~19 % of the
@@ -272,16 +205,6 @@ __device__ __forceinline__ Analysis analyse(const FPos<STM>& f, bool with_danger
     scan_dir<STM, 7>(f, kup, kdn, l, chk, pin);
   }
   asm volatile("" ::"v"(g_anti));
-#else
-  scan_dir<STM, 0>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 1>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 2>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 3>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 4>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 5>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 6>(f, kup, kdn, l, chk, pin);
-  scan_dir<STM, 7>(f, kup, kdn, l, chk, pin);
-#endif
   a.checkers = chk;
   a.pinned = pin;
   if (chk) a.cmask = chk | between(a.ksq, lsb(chk));
@@ -318,18 +241,6 @@ struct FDir {
   static constexpr u32 RQ = STM ? CR_BQ : CR_WQ;
 };
 
-// Does any lane of the wave need the attack map: a free square next to the
-// king or an open castling path (`meta`'s rights, the squares between king
-// and rook empty)?
-template <int STM>
-__device__ __forceinline__ bool wave_needs_danger(const FPos<STM>& f, u32 meta) {
-  typedef FDir<STM> FD;
-  const int h = FD::HOME;
-  const bool castle_open = ((f.K >> h) & 1) && (((meta & FD::RK) && !((f.occ >> (h + 1)) & 3)) ||
-                                                 ((meta & FD::RQ) && !((f.occ >> (h - 3)) & 7)));
-  return __ballot((king_attacks(f.K) & ~f.us) != 0 || castle_open) != 0;
-}
-
 // Castling targets (king destination squares) -- only when not in check.
 template <int STM>
 __device__ __forceinline__ u64 castle_targets(const FPos<STM>& f, const Analysis& a, u32 meta, const Board& b) {
@@ -346,22 +257,14 @@ __device__ __forceinline__ u64 castle_targets(const FPos<STM>& f, const Analysis
   return t;
 }
 
-// Number of legal moves (promotions count 4).  TAB: see king_attacks_t.
-template <int STM, bool TAB = false>
+// Number of legal moves (promotions count 4).
+template <int STM>
 __device__ __forceinline__ u32 fide_count(const Board& b, u32 meta) {
   typedef FDir<STM> FD;
   const FPos<STM> f = fpos<STM>(b);
-  // the attack map is needed only for king moves and castling: a wave none of
-  // whose lanes has a free square next to its king or an open castling path
-  // skips it (a third of perft(7)'s leaf parents; siblings share their king's
-  // surroundings)
-#if DC_FIDE_LAZY_DANGER
-  const Analysis a = analyse<STM, TAB>(f, wave_needs_danger<STM>(f, meta));
-#else
-  const Analysis a = analyse<STM, TAB>(f);
-#endif
+  const Analysis a = analyse<STM>(f);
   const u64 notus = ~f.us;
-  u32 c = pc(king_attacks_t<TAB>(f.K) & notus & ~a.danger);
+  u32 c = pc(king_attacks(f.K) & notus & ~a.danger);
   if (a.checkers & (a.checkers - 1)) return c;  // double check: king moves only
   const u64 tm = notus & a.cmask;
   // free (unpinned) pieces, one popcount per direction class
@@ -373,13 +276,9 @@ __device__ __forceinline__ u32 fide_count(const Board& b, u32 meta) {
   const u64 ce = sh<FD::CE>(Pf & kNotH) & f.them & a.cmask;
   c += pc(p1) + pc(push2) + pc(cw) + pc(ce) + 3 * (pc(p1 & FD::LAST) + pc(cw & FD::LAST) + pc(ce & FD::LAST));
   const u64 n = f.N & ~a.pinned;
-  if constexpr (TAB && (DC_FIDE_TAB_PARTS & 4)) {
-    for (u64 k = n; k; k &= k - 1) c += pc(kAtt.knight[lsb(k) & 63] & tm);
-  } else {
-    c += pc(sh<17>(n & kNotH) & tm) + pc(sh<15>(n & kNotA) & tm) + pc(sh<10>(n & kNotGH) & tm) +
-         pc(sh<6>(n & kNotAB) & tm) + pc(sh<-6>(n & kNotGH) & tm) + pc(sh<-10>(n & kNotAB) & tm) +
-         pc(sh<-15>(n & kNotH) & tm) + pc(sh<-17>(n & kNotA) & tm);
-  }
+  c += pc(sh<17>(n & kNotH) & tm) + pc(sh<15>(n & kNotA) & tm) + pc(sh<10>(n & kNotGH) & tm) +
+       pc(sh<6>(n & kNotAB) & tm) + pc(sh<-6>(n & kNotGH) & tm) + pc(sh<-10>(n & kNotAB) & tm) +
+       pc(sh<-15>(n & kNotH) & tm) + pc(sh<-17>(n & kNotA) & tm);
   const u64 e = f.empty, O = f.O & ~a.pinned, D = f.D & ~a.pinned;
   c += pc(ray_attacks<8, kAll>(O, e) & tm) + pc(ray_attacks<-8, kAll>(O, e) & tm) +
        pc(ray_attacks<1, kNotA>(O, e) & tm) + pc(ray_attacks<-1, kNotH>(O, e) & tm);
@@ -643,7 +542,7 @@ template <int STM, class SensAt, class Visit>
 __device__ __forceinline__ u32 fide_for_each_split(const Board& b, u32 meta, SensAt&& sn, Visit&& visit) {
   typedef FDir<STM> FD;
   const FPos<STM> f = fpos<STM>(b);
-  const Analysis a = analyse<STM>(f, DC_FIDE_LAZY_DANGER < 2 || wave_needs_danger<STM>(f, meta));
+  const Analysis a = analyse<STM>(f);
   const u64 notus = ~f.us;
   u32 ns = 0;
   auto emit = [&](int from, u64 targets) {
@@ -775,7 +674,7 @@ template <int STM, class SensAt>
 __device__ __forceinline__ u32 fide_count_split(const Board& b, u32 meta, SensAt&& sn, u32& ns_out) {
   typedef FDir<STM> FD;
   const FPos<STM> f = fpos<STM>(b);
-  const Analysis a = analyse<STM>(f, DC_FIDE_LAZY_DANGER < 2 || wave_needs_danger<STM>(f, meta));
+  const Analysis a = analyse<STM>(f);
   const u64 notus = ~f.us;
   u32 c = 0, ns = 0;
   if (a.ksq >= 0) {

@@ -63,7 +63,7 @@ enum : int {
   T_NULL,       // {"piece":null},   (the last cell of a row drops the comma)
   T_CELL0,      // {"piece":{"color":0,"kind":"P"}},  ... 12 cells: colour-major P N B R Q K
   T_NULLRUN = T_CELL0 + 12,  // T_NULL eight times: a run of k empty cells is its first 15 k bytes
-  T_BOARD_ROW,  // ","board":{"rows":[{"cells":[   (T_BOARD + T_ROW: DC_HASH_MERGE)
+  T_BOARD_ROW,  // ","board":{"rows":[{"cells":[   (T_BOARD + T_ROW, round 6)
   T_ROW_SEP,    // ]},{"cells":[                  (T_ROW_END + T_ROW)
   T_LAST,       // ]}]}}                          (the last row's end + T_END)
   T_COUNT
@@ -115,50 +115,33 @@ static_assert(cells_even(), "the 12 piece-cell templates are consecutive and of 
 constexpr u32 kNullRunOff = kJsonTpl.off[T_NULLRUN];
 static_assert(kJsonTpl.len[T_NULLRUN] == 8 * kCellNullLen, "eight null cells");
 static_assert(kNullRunOff + 8 * kCellNullLen + 8 <= sizeof(kJsonTpl.s), "copy8 may read 7 bytes past a piece");
-// DC_HASH_NULLRUN (round 6): a run of empty cells in a row is one piece (the
-// first 15 k bytes of T_NULLRUN), so the board's ~32 empty cells take ~10
-// trips of the fill loop instead of 32.
-#ifndef DC_HASH_NULLRUN
-#define DC_HASH_NULLRUN 1
-#endif
-// DC_HASH_MERGE (round 6): fewer trips of the fill loop -- the row boundaries
-// as one piece each (T_BOARD_ROW, T_ROW_SEP, T_LAST instead of two), and up to
-// two accepted moves' tokens per token piece.
-#ifndef DC_HASH_MERGE
-#define DC_HASH_MERGE 1
-#endif
-// DC_HASH_TOK3 (round 6): three tokens per piece while the move numbers are
-// BCD (a token then has at most 15 bytes), two otherwise; the token area grows
-// to 46 B a lane and the block rows shrink to 144 B to keep three blocks' LDS
-// under 160 KB.
-#ifndef DC_HASH_TOK3
-#define DC_HASH_TOK3 1
-#endif
-constexpr u32 kTokPerPiece = DC_HASH_MERGE ? 2 : 1;
-// DC_HASH_PF (round 6): with the replay pre-pass (info), the token loop takes
-// each ply's info byte and move word from a queue of DC_HASH_PF plies loaded
-// ahead (0: loaded where used, the move's load waiting on the info byte's).
-// Same box, alternating: 4 against 0, kernel 3.26-3.29 -> 3.15-3.20 ms
+// Round 6, fewer trips of the fill loop (each step was a compile-time switch
+// while it was measured):
+//  - a run of empty cells in a row is one piece (the first 15 k bytes of
+//    T_NULLRUN), so the board's ~32 empty cells take ~10 trips instead of 32;
+//  - the row boundaries are one piece each (T_BOARD_ROW, T_ROW_SEP, T_LAST
+//    instead of two), and a token piece holds up to two accepted moves' tokens;
+//  - three tokens per piece while the move numbers are BCD (a token then has at
+//    most 15 bytes), two otherwise; the token area grew to 46 B a lane and the
+//    block rows shrank to 144 B to keep three blocks' LDS under 160 KB.
+constexpr u32 kTokPerPiece = 2;
+// Round 6: with the replay pre-pass (info), the token loop takes each ply's
+// info byte and move word from a queue of kHashPf plies loaded ahead (before:
+// loaded where used, the move's load waiting on the info byte's).  Same box,
+// alternating: 4 against none, kernel 3.26-3.29 -> 3.15-3.20 ms
 // (profiles/r06/ab_hash_pf.txt); 8 against 4 within 0.5 % (ab_hash_pf8.txt).
-#ifndef DC_HASH_PF
-#define DC_HASH_PF 4
-#endif
-// DC_HASH_P1 (round 6): pass 1's parity of the accepted plies reads this many
-// info bytes per batch of loads (1: one load, one wait per ply).  16 against
-// 1, same box, alternating: kernel 3.08-3.10 -> 2.92-2.95 ms
+constexpr int kHashPf = 4;
+// Round 6: pass 1's parity of the accepted plies reads this many info bytes
+// per batch of loads (before: one load, one wait per ply).  16 against 1, same
+// box, alternating: kernel 3.08-3.10 -> 2.92-2.95 ms
 // (profiles/r06/ab_hash_p1.txt): every wave of a round starts with this loop
 // at once, so its round trips had nothing to overlap.  40 measured slower
 // than 16 (2.97-3.02 against 2.92-2.98 ms, ab_hash_p1_40.txt).
-#ifndef DC_HASH_P1
-#define DC_HASH_P1 16
-#endif
-// DC_HASH_GLB8 (round 6): pieces in global memory (the names, the start
-// history) are copied 8 loads at a time instead of one load and wait a byte.
+constexpr int kHashP1 = 16;
+// Tried and dropped (round 6): copying the pieces in global memory (the names,
+// the start history) 8 loads at a time instead of one load and wait a byte.
 // Same box, alternating: kernel 2.92-2.94 ms either way (the names are ~24
-// bytes a game; profiles/r06/ab_hash_glb8.txt), so off.
-#ifndef DC_HASH_GLB8
-#define DC_HASH_GLB8 0
-#endif
+// bytes a game; profiles/r06/ab_hash_glb8.txt).
 
 // kind code (dc_ref.h: P=1 N=2 K=3 X=4 B=5 R=6 Q=7) -> index in P N B R Q K; 6 = unknown
 __device__ __forceinline__ u32 kind_index(u32 code) {
@@ -175,25 +158,19 @@ __device__ __forceinline__ u32 bcd_add2(u32 a) {
 
 constexpr u32 kHashThreads = 256;
 // one token is at most 18 bytes (" " + 10 digits + ". " + kind + file + "x" +
-// square); 36 B holds two and keeps three 256-thread blocks' LDS under 160 KB
-constexpr u32 kTokBytes = DC_HASH_TOK3 ? 46 : 36;
+// square); 46 B holds three BCD-numbered ones (15 bytes each) or two of any kind
+constexpr u32 kTokBytes = 46;
 constexpr u32 kAccPlies = 128;  // per-lane verdict bits kept from pass 1 (4 dwords of LDS)
-// DC_HASH_COPY8 (round 5): pieces whose bytes sit in LDS (templates, move
+// Round 5: pieces whose bytes sit in LDS (templates, move
 // tokens) are copied 8 bytes a step -- eight ds_read_u8 then eight ds_write_b8
 // at immediate offsets, one wait -- instead of a generic-pointer byte loop that
 // waits on every byte.  A step may read up to 7 bytes past its piece (LDS: in
 // the block's allocation, or 0 past it) and write up to 7 past the block's
 // byte 135, so each lane's block row is kBlkRow (>= 143) bytes; the bytes
 // written past a piece are overwritten by the next piece or by the padding.
-#ifndef DC_HASH_COPY8
-#define DC_HASH_COPY8 1
-#endif
-// DC_HASH_FUSE (round 5): a piece fetched in the fill loop is copied in the
+// Round 5: a piece fetched in the fill loop is copied in the
 // same trip (round 4 spent one trip on the fetch and the next on the copy).
-#ifndef DC_HASH_FUSE
-#define DC_HASH_FUSE 1
-#endif
-constexpr u32 kBlkRow = DC_HASH_COPY8 ? (DC_HASH_TOK3 ? 144 : 152) : kKeccakRate;  // 152 = 38 dwords: 2-way banks for the u64 absorb reads
+constexpr u32 kBlkRow = 144;
 
 // Stages of a lane's JSON stream (in order).
 enum : u32 {
@@ -228,18 +205,16 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
   // parity and pass 2 reads kind and capture from it; no ply is validated here
   u32 stm = stm0;
   if (active && info) {
-    // DC_HASH_P1 bytes loaded before any is used (round 6: one at a time, the
+    // kHashP1 bytes loaded before any is used (round 6: one at a time, the
     // loop waited a memory round trip per ply, every wave of a round at once)
     u32 p = 0;
-#if DC_HASH_P1 > 1
-    for (; p + DC_HASH_P1 <= n_plies; p += DC_HASH_P1) {
-      u32 cb[DC_HASH_P1];
+    for (; p + kHashP1 <= n_plies; p += kHashP1) {
+      u32 cb[kHashP1];
 #pragma unroll
-      for (int j = 0; j < DC_HASH_P1; ++j) cb[j] = info[(size_t)(p + j) * n_games + g];
+      for (int j = 0; j < kHashP1; ++j) cb[j] = info[(size_t)(p + j) * n_games + g];
 #pragma unroll
-      for (int j = 0; j < DC_HASH_P1; ++j) stm ^= (u32)(cb[j] != 0xFFu);
+      for (int j = 0; j < kHashP1; ++j) stm ^= (u32)(cb[j] != 0xFFu);
     }
-#endif
     for (; p < n_plies; ++p) stm ^= (u32)(info[(size_t)p * n_games + g] != 0xFFu);
   } else if (active) {
     Board b = start;
@@ -289,10 +264,9 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
     wn1 = names_off[2 * g + 1];
     bn1 = names_off[2 * g + 2];
   }
-#if DC_HASH_PF
-  u32 pq_c[DC_HASH_PF], pq_m[DC_HASH_PF];  // plies ply .. ply + DC_HASH_PF - 1 (clamped to the last)
+  u32 pq_c[kHashPf], pq_m[kHashPf];  // plies ply .. ply + kHashPf - 1 (clamped to the last)
 #pragma unroll
-  for (int j = 0; j < DC_HASH_PF; ++j) {
+  for (int j = 0; j < kHashPf; ++j) {
     pq_c[j] = pq_m[j] = 0;
     if (info && active && n_plies) {
       const u32 pn = min((u32)j, n_plies - 1);
@@ -300,7 +274,6 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
       pq_m[j] = moves[(size_t)pn * n_games + g];
     }
   }
-#endif
   const u32 tok_off = kTplBytes + tid * kTokBytes;
   char* mytok = lpool + tok_off;
   auto tpl_piece = [&](int i, u32 drop) {
@@ -334,25 +307,23 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
           // the next accepted moves (up to kTokPerPiece): their tokens "[ ]N. san"
           rem = 0;
           u32 n = 0, got = 0;
-          const u32 tok_max = (DC_HASH_TOK3 && bcd_ok) ? 3u : kTokPerPiece;  // kernel-uniform
+          const u32 tok_max = bcd_ok ? 3u : kTokPerPiece;  // kernel-uniform
           while (ply < n_plies && got < tok_max) {
             const u32 p = ply++;
             u32 code = 0, m = 0;
-#if DC_HASH_PF
             if (info) {  // kernel-uniform
               code = pq_c[0];
               m = pq_m[0];
 #pragma unroll
-              for (int j = 0; j + 1 < DC_HASH_PF; ++j) {
+              for (int j = 0; j + 1 < kHashPf; ++j) {
                 pq_c[j] = pq_c[j + 1];
                 pq_m[j] = pq_m[j + 1];
               }
-              const u32 pn = min(p + DC_HASH_PF, n_plies - 1);
-              pq_c[DC_HASH_PF - 1] = info[(size_t)pn * n_games + g];
-              pq_m[DC_HASH_PF - 1] = moves[(size_t)pn * n_games + g];
+              const u32 pn = min(p + kHashPf, n_plies - 1);
+              pq_c[kHashPf - 1] = info[(size_t)pn * n_games + g];
+              pq_m[kHashPf - 1] = moves[(size_t)pn * n_games + g];
               if (code == 0xFFu) continue;  // rejected
             } else
-#endif
             {
               if (info) {  // kernel-uniform
                 code = info[(size_t)p * n_games + g];
@@ -404,14 +375,9 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
             loff = tok_off;
             rem = n;
           } else {
-#if DC_HASH_MERGE
             stage = S_ROW;  // the board's header and its first row's (row 0)
             row = 0;
             tpl_piece(T_BOARD_ROW, 0);
-#else
-            stage = S_BOARD;
-            tpl_piece(T_BOARD, 0);
-#endif
           }
           break;
         }
@@ -433,7 +399,6 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
         case S_ROW:
         case S_CELL: {
           if (stage == S_CELL && col == 7) {
-#if DC_HASH_MERGE
             if (row == 7) {  // the last row's end and the board's and object's
               stage = S_END;
               tpl_piece(T_LAST, 0);
@@ -442,15 +407,10 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
               stage = S_ROW;
               tpl_piece(T_ROW_SEP, 0);
             }
-#else
-            stage = S_ROW_END;
-            tpl_piece(T_ROW_END, row == 7 ? 1u : 0u);
-#endif
             break;
           }
           col = stage == S_ROW ? 0u : col + 1;
           stage = S_CELL;
-#if DC_HASH_NULLRUN
           {
             // empty cells from col on in this row (bit 8 stops the run at the row's end)
             const u32 occ8 = (u32)(occupied(b) >> (8 * row)) & 0xFFu;
@@ -463,7 +423,6 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
               break;
             }
           }
-#endif
           const u32 nib = nibble(b, (int)(8 * row + col));
           const u32 ki = kind_index(nib >> 1);
           // the cell templates' offsets and lengths as constants (round 6:
@@ -495,30 +454,13 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
       while (fill < (u32)kKeccakRate && stage != S_DONE) {
         if (rem == 0) {
           next_piece();  // the next non-empty piece, or the stream's end
-#if DC_HASH_FUSE
           if (stage == S_DONE) break;  // (the fetch falls through to the copy: one loop trip per piece)
-#else
-          continue;
-#endif
         }
         const u32 n = min(rem, (u32)kKeccakRate - fill);
         if (glb) {
-#if DC_HASH_GLB8
-          // 8 loads issued before any store (clamped to the piece's last byte;
-          // the up to 7 bytes written past it are overwritten, as in COPY8)
-          for (u32 k = 0; k < n; k += 8) {
-            char v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = src[min(k + (u32)j, n - 1)];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) my[fill + k + j] = (uint8_t)v[j];
-          }
-#else
           for (u32 k = 0; k < n; ++k) my[fill + k] = (uint8_t)src[k];
-#endif
           src += n;
         } else {
-#if DC_HASH_COPY8
           for (u32 k = 0; k < n; k += 8) {
             const char* a = lpool + loff + k;
             uint8_t* d = my + fill + k;
@@ -528,9 +470,6 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
 #pragma unroll
             for (int j = 0; j < 8; ++j) d[j] = (uint8_t)v[j];
           }
-#else
-          for (u32 k = 0; k < n; ++k) my[fill + k] = (uint8_t)lpool[loff + k];
-#endif
           loff += n;
         }
         rem -= n;

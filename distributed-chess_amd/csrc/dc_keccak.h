@@ -126,25 +126,20 @@ __device__ __forceinline__ void keccak_f1600_dev(uint64_t* a64) {
   K64 a[25];
 #pragma unroll
   for (int i = 0; i < 25; ++i) a[i] = K64{(uint32_t)a64[i], (uint32_t)(a64[i] >> 32)};
-// DC_KECCAK_UNROLL (round 6 A/B): rounds per loop trip.  2 and 4 fit the same
-// 3 waves/SIMD (142-144 VGPRs) and measured slower: hash kernel 3.90-3.93 ->
-// 3.99-4.00 ms (2) and 3.93-4.00 ms (4) (profiles/r06/ab_keccak_unroll.txt).
-#ifndef DC_KECCAK_UNROLL
-#define DC_KECCAK_UNROLL 1
-#endif
-// DC_KECCAK_FUSE (round 6): theta without D (see the round body): same box,
-// alternating, hash kernel 3.18-3.20 -> 3.10-3.12 ms (profiles/r06/ab_keccak_fuse.txt).
-#ifndef DC_KECCAK_FUSE
-#define DC_KECCAK_FUSE 1
-#endif
-#pragma unroll DC_KECCAK_UNROLL
+  // Rounds per loop trip (round 6 A/B).  2 and 4 fit the same 3 waves/SIMD
+  // (142-144 VGPRs) and measured slower: hash kernel 3.90-3.93 -> 3.99-4.00 ms
+  // (2) and 3.93-4.00 ms (4) (profiles/r06/ab_keccak_unroll.txt).
+  constexpr int kKeccakUnroll = 1;
+  // Theta without D (round 6, see the round body) against forming D first: same
+  // box, alternating, hash kernel 3.18-3.20 -> 3.10-3.12 ms
+  // (profiles/r06/ab_keccak_fuse.txt).
+#pragma unroll kKeccakUnroll
   for (int r = 0; r < 24; ++r) {
     const K64 c0 = kx3(kx3(a[0], a[5], a[10]), a[15], a[20]);
     const K64 c1 = kx3(kx3(a[1], a[6], a[11]), a[16], a[21]);
     const K64 c2 = kx3(kx3(a[2], a[7], a[12]), a[17], a[22]);
     const K64 c3 = kx3(kx3(a[3], a[8], a[13]), a[18], a[23]);
     const K64 c4 = kx3(kx3(a[4], a[9], a[14]), a[19], a[24]);
-#if DC_KECCAK_FUSE
     // theta's D[x] = C[x-1] ^ rot1(C[x+1]) is never formed: each lane takes
     // a ^ C[x-1] ^ rot1(C[x+1]) as one three-input xor (180 VALU a round, not 190)
     const K64 r0 = krot<1>(c0), r1 = krot<1>(c1), r2 = krot<1>(c2), r3 = krot<1>(c3), r4 = krot<1>(c4);
@@ -154,16 +149,6 @@ __device__ __forceinline__ void keccak_f1600_dev(uint64_t* a64) {
 #define DC_KD2 c1, r3
 #define DC_KD3 c2, r4
 #define DC_KD4 c3, r0
-#else
-    const K64 d0 = kx2(c4, krot<1>(c1)), d1 = kx2(c0, krot<1>(c2)), d2 = kx2(c1, krot<1>(c3));
-    const K64 d3 = kx2(c2, krot<1>(c4)), d4 = kx2(c3, krot<1>(c0));
-#define DC_KTH(i, d) kx2(a[i], d)
-#define DC_KD0 d0
-#define DC_KD1 d1
-#define DC_KD2 d2
-#define DC_KD3 d3
-#define DC_KD4 d4
-#endif
 #define DC_KT(i, D) DC_KTH(i, D)
     K64 b[25];
     b[0] = DC_KT(0, DC_KD0);

@@ -12,10 +12,10 @@
 // (S = true) collects that run in LDS, kStageChunk moves at a time, at the
 // lanes' wave-prefix offsets, and streams it out as aligned dwords (an odd
 // first or last u16 goes out on its own); the plain emit (S = false) stores
-// each move straight from its lane.  DC_LEGAL_STAGED picks the shipped one;
-// the A/B build holds both (DC_LEGAL_EMIT=plain|staged).  The plain emit
-// ships: at 1M positions it took 0.51 ms against the staged one's 0.74 ms
-//  -- the kernel is bound by re-deriving the moves
+// each move straight from its lane.  The plain emit ships; the A/B build also
+// holds the staged one (DC_LEGAL_EMIT=plain|staged).  Why plain: at 1M
+// positions it took 0.51 ms against the staged one's 0.74 ms (DESIGN.md
+// section 3.10) -- the kernel is bound by re-deriving the moves
 // piece by piece, not by its stores, and staging adds LDS traffic, two wave
 // syncs per chunk and a second enumeration for lanes that straddle chunks.
 //
@@ -24,10 +24,6 @@
 
 #include "dc_common.h"
 #include "dc_movegen.h"
-
-#ifndef DC_LEGAL_STAGED
-#define DC_LEGAL_STAGED 0
-#endif
 
 namespace dc {
 
@@ -354,13 +350,13 @@ __global__ __launch_bounds__(kLegalBlock) void k_legal_small(const DevPos* __res
   legal_publish_done(done, seq);
 }
 
-// the A/B build holds both emit variants; the product only the shipped one
+// the A/B build holds both emit variants; the product only the plain one
 __host__ inline bool use_staged(bool plain) {
 #ifdef DC_AB_KNOBS
   if (ab_env("DC_LEGAL_EMIT")) return !plain;
 #endif
   (void)plain;
-  return DC_LEGAL_STAGED != 0;
+  return false;
 }
 
 }  // namespace
@@ -371,18 +367,16 @@ hipError_t launch_legal_small(hipStream_t st, u32 rules, const DevPos* pos, u32 
   const bool staged = use_staged(plain);
 #define DC_LEGAL_SMALL(G, S) \
   hipLaunchKernelGGL((k_legal_small<G, S>), dim3(1), dim3(kLegalBlock), 0, st, pos, n, offsets, status, moves, cap, total, done, seq)
-#if defined(DC_AB_KNOBS) || DC_LEGAL_STAGED
+#ifdef DC_AB_KNOBS
   if (staged) {
     if (rules == 0) DC_LEGAL_SMALL(RefGen, true);
     else DC_LEGAL_SMALL(FideGen, true);
   }
 #endif
-#if defined(DC_AB_KNOBS) || !DC_LEGAL_STAGED
   if (!staged) {
     if (rules == 0) DC_LEGAL_SMALL(RefGen, false);
     else DC_LEGAL_SMALL(FideGen, false);
   }
-#endif
 #undef DC_LEGAL_SMALL
   return hipGetLastError();
 }
@@ -417,18 +411,16 @@ hipError_t launch_legal_emit(hipStream_t st, u32 rules, const DevPos* pos, u32 n
   const bool staged = use_staged(plain);
 #define DC_LEGAL_EMIT(G, S) \
   hipLaunchKernelGGL((k_legal_emit<G, S>), grid, dim3(kLegalBlock), 0, st, pos, n, offsets, block_sum, block_base, moves, limit)
-#if defined(DC_AB_KNOBS) || DC_LEGAL_STAGED
+#ifdef DC_AB_KNOBS
   if (staged) {
     if (rules == 0) DC_LEGAL_EMIT(RefGen, true);
     else DC_LEGAL_EMIT(FideGen, true);
   }
 #endif
-#if defined(DC_AB_KNOBS) || !DC_LEGAL_STAGED
   if (!staged) {
     if (rules == 0) DC_LEGAL_EMIT(RefGen, false);
     else DC_LEGAL_EMIT(FideGen, false);
   }
-#endif
 #undef DC_LEGAL_EMIT
   return hipGetLastError();
 }

@@ -62,22 +62,15 @@ struct PawnDir {
   static constexpr u64 ROW_DBL = STM ? kRow(4) : kRow(3);     // ... and double pushes land here
 };
 
-// Moves of the king(s) onto `allowed`.  One king (the norm): the 3x3 pattern
-// shifted to its square, with the wrap file masked -- one variable 64-bit
-// shift instead of eight.  Several kings (possible through the cells adapter)
-// fall back to per-direction popcounts.
+// Moves of the king(s) onto `allowed`.  One king (the norm): its kAtt row (up
+// to round 3 the 3x3 pattern shifted to its square with the wrap file masked;
+// the table won the round-4 A/B, see kAtt).  Several kings (possible through
+// the cells adapter) fall back to per-direction popcounts.
 __device__ __forceinline__ u32 king_moves(u64 k, u64 allowed) {
   if ((k & (k - 1)) == 0) {
     if (!k) return 0;
     const int s = lsb(k);
-#if DC_ATT_TAB
     return pc(kAtt.king[s & 63] & allowed);  // (& 63: the load may be speculated above the k == 0 exit)
-#endif
-    constexpr u64 kAtB2 = 0x0000000000070507ull;  // a1 b1 c1 a2 c2 a3 b3 c3 around b2 (9)
-    const u64 att = s >= 9 ? (kAtB2 << (s - 9)) : (kAtB2 >> (9 - s));
-    const int f = s & 7;
-    const u64 wrap = f == 0 ? kNotH : (f == 7 ? kNotA : kAll);
-    return pc(and3(att, wrap, allowed));
   }
   return pc(sh<8>(k) & allowed) + pc(sh<-8>(k) & allowed) + pc(and3(sh<1>(k), kNotA, allowed)) +
          pc(and3(sh<-1>(k), kNotH, allowed)) + pc(and3(sh<9>(k), kNotA, allowed)) +
@@ -87,21 +80,11 @@ __device__ __forceinline__ u32 king_moves(u64 k, u64 allowed) {
 
 // Knight moves onto `allowed`: per knight one kAtt row and one popcount (the
 // norm is at most two knights: ~26 VALU against 40 for the eight direction
-// terms).  DC_KNIGHT_TAB=0: the direction terms (A/B).
-#ifndef DC_KNIGHT_TAB
-#define DC_KNIGHT_TAB 1
-#endif
+// terms, which lost the A/B and are gone).
 __device__ __forceinline__ u32 knight_moves(u64 n, u64 allowed) {
-#if DC_KNIGHT_TAB
   u32 c = 0;
   for (; n; n &= n - 1) c += pc(kAtt.knight[lsb(n) & 63] & allowed);
   return c;
-#else
-  return pc(and3(sh<17>(n), kNotA, allowed)) + pc(and3(sh<15>(n), kNotH, allowed)) +
-         pc(and3(sh<10>(n), kNotAB, allowed)) + pc(and3(sh<6>(n), kNotGH, allowed)) +
-         pc(and3(sh<-6>(n), kNotAB, allowed)) + pc(and3(sh<-10>(n), kNotGH, allowed)) +
-         pc(and3(sh<-15>(n), kNotA, allowed)) + pc(and3(sh<-17>(n), kNotH, allowed));
-#endif
 }
 
 // Bulk count of REF moves for the side to move: the number of (from,to) pairs
@@ -305,26 +288,10 @@ __device__ __forceinline__ u32 ref_count_nonpawn_g(const Board& b, u64& att, u64
   return c + diag;
 }
 
-// Knight and king attack sets of one square: the pattern around c3 / b2
-// shifted to s, the files a shift wraps into masked (king_moves' trick).
-__device__ __forceinline__ u64 knight_att_sq(int s) {
-#if DC_ATT_TAB
-  return kAtt.knight[s];
-#endif
-  constexpr u64 kAtC3 = 0x0000000A1100110Aull;  // b1 d1 a2 e2 a4 e4 b5 d5 around c3 (18)
-  const u64 a = s >= 18 ? (kAtC3 << (s - 18)) : (kAtC3 >> (18 - s));
-  const int f = s & 7;
-  return a & (f <= 1 ? kNotGH : (f >= 6 ? kNotAB : kAll));
-}
-__device__ __forceinline__ u64 king_att_sq(int s) {
-#if DC_ATT_TAB
-  return kAtt.king[s];
-#endif
-  constexpr u64 kAtB2 = 0x0000000000070507ull;
-  const u64 a = s >= 9 ? (kAtB2 << (s - 9)) : (kAtB2 >> (9 - s));
-  const int f = s & 7;
-  return a & (f == 0 ? kNotH : (f == 7 ? kNotA : kAll));
-}
+// Knight and king attack sets of one square (kAtt rows; before round 4 the
+// pattern around c3 / b2 shifted to s with the wrapped files masked).
+__device__ __forceinline__ u64 knight_att_sq(int s) { return kAtt.knight[s]; }
+__device__ __forceinline__ u64 king_att_sq(int s) { return kAtt.king[s]; }
 
 // count_O of the child P∘(f -> t) (the other side's move; O = SIDE to move in
 // the child) when O's orthogonal group is unchanged (f, t off `orth` of
@@ -391,19 +358,9 @@ __device__ __forceinline__ u32 ref_pawn_count_child(const Board& b, int f, int t
 // (mid squares are push squares), so a quiet move with f, t outside G leaves
 // SIDE's pawn count unchanged -- and the correction case has t or f on a mid
 // square, inside G.
-template <int SIDE>
-__device__ __forceinline__ u64 ref_pawn_sensitive(const Board& b, u32& pawn_cnt) {
-  typedef PawnDir<SIDE> PD;
-  const Sides s = sides<SIDE>(b);
-  const u64 q1 = sh<PD::F>(s.P);
-  const u64 cw = sh<PD::CW>(s.P) & kNotH, ce = sh<PD::CE>(s.P) & kNotA;
-  const u64 push1 = q1 & s.empty;
-  const u64 land = sh<PD::F>(push1) & PD::ROW_DBL;  // landings whose mid is empty
-  pawn_cnt = pc(or_and(push1, land, s.empty)) + pc(cw & s.enemy) + pc(ce & s.enemy);
-  return bop3<0xFE>(q1, cw, ce) | land;
-}
-
-// ref_pawn_sensitive plus the weight planes of g on the parent (DC_C2C_GCORR):
+// ref_pawn_planes returns G and SIDE's pawn-move count (up to round 4 a
+// ref_pawn_sensitive did only that), plus, since round 5, the weight planes of
+// g on the parent:
 //   g(x) = [x in cw] + [x in ce] - [x in q1] - [x in mid] - [x in land]
 // (cw/ce: SIDE's pawn capture squares, q1: its push squares, mid: middle
 // squares of a double push whose landing is empty, land: landings whose
@@ -473,7 +430,7 @@ __device__ __forceinline__ void ray_attacks2(u64 g1, u64 g2, u64 empty, u64& r1,
 }
 
 // Everything k_count2c needs per parent P (side STM to move, opponent O):
-//   base, att = ref_count_nonpawn<O>;  pawn_o (and G) = ref_pawn_sensitive<O>;
+//   base, att = ref_count_nonpawn<O>;  pawn_o (and G) = ref_pawn_planes<O>;
 //   Fs = own & ~(att | G), Ts = empty & ~(att | G);
 //   n_total = ref_count<STM>, n_simple = ref_count_simple<STM>(Fs, Ts),
 // with STM's all-source and Fs-source fills fused per direction.  Computed
@@ -492,20 +449,16 @@ struct ParentSplit {
 // simple targets are also counted on the g = +1 and g = -1 planes.  80 % of
 // the quiet children round 4 enumerated for a pawn recount become simple
 // (tools/ref_gsplit_proto.py).
-#ifndef DC_C2C_GCORR
-#define DC_C2C_GCORR 1
-#endif
-
+//
 // GROUPS: also orth/diag (ref_count_nonpawn_g) for the group-wise recount.
 // TGT: also the side to move's slider target sets per direction (tgt[0..7]
 // in ref_for_each_special's slide order), so the enumeration of the special
-// moves reuses these fills instead of running them again (DC_C2C_REUSE).
+// moves reuses these fills instead of running them again.
 template <int STM, bool GROUPS = false, bool TGT = false>
 __device__ __forceinline__ void ref_parent_split(const Board& b, ParentSplit& r, u64* tgt = nullptr) {
   if constexpr (GROUPS) r.base = ref_count_nonpawn_g<1 - STM>(b, r.att, r.orth, r.diag);
   else r.base = ref_count_nonpawn<1 - STM>(b, r.att);
   const Sides s = sides<STM>(b);
-#if DC_C2C_GCORR
   u64 P1, N1, BIG;
   const u64 Fs = s.own & ~(r.att | ref_pawn_planes<1 - STM>(b, r.pawn_o, P1, N1, BIG));
   const u64 Ts = s.empty & ~(r.att | BIG), no = s.notown;
@@ -515,11 +468,6 @@ __device__ __forceinline__ void ref_parent_split(const Board& b, ParentSplit& r,
     gp += pc(x & P1);
     gn += pc(x & N1);
   };
-#else
-  const u64 keep = ~(r.att | ref_pawn_sensitive<1 - STM>(b, r.pawn_o));
-  const u64 Fs = s.own & keep, Ts = s.empty & keep, no = s.notown;
-  auto wgt = [](u64) {};
-#endif
   r.Fs = Fs;
   r.Ts = Ts;
   u64 e = s.empty;
@@ -533,7 +481,6 @@ __device__ __forceinline__ void ref_parent_split(const Board& b, ParentSplit& r,
   wgt(pm);
   t += pc(and3(sh<PD::CW>(s.P), kNotH, s.enemy)) + pc(and3(sh<PD::CE>(s.P), kNotA, s.enemy));
   using std::integral_constant;
-#if DC_KNIGHT_TAB
   // per knight: its kAtt row counts toward t and, from a source in Fs, m
   for (u64 n = s.N; n; n &= n - 1) {
     const int f = lsb(n) & 63;
@@ -543,25 +490,7 @@ __device__ __forceinline__ void ref_parent_split(const Board& b, ParentSplit& r,
     m += pc(x);
     wgt(x);
   }
-#else
-  const u64 n = s.N, ns = s.N & Fs;
-  auto leap = [&](auto dtag, u64 guard) {
-    constexpr int D = decltype(dtag)::value;
-    t += pc(and3(sh<D>(n), guard, no));
-    const u64 x = and3(sh<D>(ns), guard, Ts);
-    m += pc(x);
-    wgt(x);
-  };
-  leap(integral_constant<int, 17>{}, kNotA);
-  leap(integral_constant<int, 15>{}, kNotH);
-  leap(integral_constant<int, 10>{}, kNotAB);
-  leap(integral_constant<int, 6>{}, kNotGH);
-  leap(integral_constant<int, -6>{}, kNotAB);
-  leap(integral_constant<int, -10>{}, kNotGH);
-  leap(integral_constant<int, -15>{}, kNotA);
-  leap(integral_constant<int, -17>{}, kNotH);
-#endif
-  if (DC_ATT_TAB && (s.K & (s.K - 1)) == 0) {  // one king (or none): one attack set for both counts
+  if ((s.K & (s.K - 1)) == 0) {  // one king (or none): one attack set for both counts
     const u64 ka = s.K ? kAtt.king[lsb(s.K) & 63] : 0ull;
     t += pc(ka & no);
     const u64 x = (s.K & Fs) ? ka & Ts : 0ull;
@@ -570,13 +499,8 @@ __device__ __forceinline__ void ref_parent_split(const Board& b, ParentSplit& r,
   } else {
     t += king_moves(s.K, no);
     m += king_moves(s.K & Fs, Ts);
-#if DC_C2C_GCORR
     for (u64 k = s.K & Fs; k; k &= k - 1) wgt(king_att_sq(lsb(k)) & Ts);  // several kings (cells adapter)
-#endif
   }
-#ifndef DC_C2C_KSKIP
-#define DC_C2C_KSKIP 1
-#endif
   // KSKIP: the simple moves' fill (from the sliders in Fs) differs from the
   // full one only where a slider stands on a K square (off Fs); a wave none of
   // whose lanes has such a slider in the class skips that second fill
@@ -616,32 +540,24 @@ __device__ __forceinline__ void ref_parent_split(const Board& b, ParentSplit& r,
   };
   using T2 = std::true_type;
   using T1 = std::false_type;
-  if (!DC_C2C_KSKIP || __ballot((s.O & ~Fs) != 0) != 0) orth(T2{});
+  if (__ballot((s.O & ~Fs) != 0) != 0) orth(T2{});
   else orth(T1{});
-  if (!DC_C2C_KSKIP || __ballot((s.D & ~Fs) != 0) != 0) diag(T2{});
+  if (__ballot((s.D & ~Fs) != 0) != 0) diag(T2{});
   else diag(T1{});
   r.n_total = t;
   r.n_simple = m;
-#if DC_C2C_GCORR
   r.gcorr = gp - gn;
-#else
-  r.gcorr = 0;
-#endif
 }
 
 // The knight and king moves of ref_for_each_special(_pre), in one order both
-// share.  DC_ENUM_PIECE (round 4): per piece -- the source's attack set from
+// share.  Per piece (round 4) -- the source's attack set from
 // kAtt, its special targets (not both f in Fs and t in Ts) walked in one loop --
 // instead of one loop per direction: a wave pays the slowest lane of every
 // loop it enters, and 16 direction loops (each with its own setup) cost more
 // than 2-3 piece loops (tools/bbprof_inline.py: the enumeration was 25 % of
 // k_count3c's VALU issue cycles).
-#ifndef DC_ENUM_PIECE
-#define DC_ENUM_PIECE 1
-#endif
-template <class Leap, class Visit>
-__device__ __forceinline__ void special_leapers(u64 n, u64 k, u64 no, u64 Fs, u64 Ts, Leap&& leap, Visit&& visit) {
-#if DC_ENUM_PIECE
+template <class Visit>
+__device__ __forceinline__ void special_leapers(u64 n, u64 k, u64 no, u64 Fs, u64 Ts, Visit&& visit) {
   auto piece = [&](int f, u64 att) {
     const u64 simple = ((Fs >> f) & 1) ? Ts : 0ull;
     u64 targets = att & no & ~simple;
@@ -659,25 +575,6 @@ __device__ __forceinline__ void special_leapers(u64 n, u64 k, u64 no, u64 Fs, u6
     const int f = lsb(k);
     piece(f, kAtt.king[f]);
   }
-#else
-  (void)visit;
-  leap(sh<17>(n & kNotH) & no, 17, sh<17>(Fs) & Ts);
-  leap(sh<15>(n & kNotA) & no, 15, sh<15>(Fs) & Ts);
-  leap(sh<10>(n & kNotGH) & no, 10, sh<10>(Fs) & Ts);
-  leap(sh<6>(n & kNotAB) & no, 6, sh<6>(Fs) & Ts);
-  leap(sh<-6>(n & kNotGH) & no, -6, sh<-6>(Fs) & Ts);
-  leap(sh<-10>(n & kNotAB) & no, -10, sh<-10>(Fs) & Ts);
-  leap(sh<-15>(n & kNotH) & no, -15, sh<-15>(Fs) & Ts);
-  leap(sh<-17>(n & kNotA) & no, -17, sh<-17>(Fs) & Ts);
-  leap(sh<8>(k) & no, 8, sh<8>(Fs) & Ts);
-  leap(sh<-8>(k) & no, -8, sh<-8>(Fs) & Ts);
-  leap(sh<1>(k & kNotH) & no, 1, sh<1>(Fs) & Ts);
-  leap(sh<-1>(k & kNotA) & no, -1, sh<-1>(Fs) & Ts);
-  leap(sh<9>(k & kNotH) & no, 9, sh<9>(Fs) & Ts);
-  leap(sh<7>(k & kNotA) & no, 7, sh<7>(Fs) & Ts);
-  leap(sh<-7>(k & kNotH) & no, -7, sh<-7>(Fs) & Ts);
-  leap(sh<-9>(k & kNotA) & no, -9, sh<-9>(Fs) & Ts);
-#endif
 }
 
 // ref_for_each_move<STM> without the simple moves (source in Fs, target in
@@ -702,7 +599,7 @@ __device__ __forceinline__ void ref_for_each_special(const Board& b, u64 Fs, u64
   leap(sh<PD::F>(push1 & PD::ROW_AFTER1) & e, 2 * PD::F, sh<2 * PD::F>(Fs) & Ts);
   leap(sh<PD::CW>(s.P & kNotA) & s.enemy, PD::CW, 0);
   leap(sh<PD::CE>(s.P & kNotH) & s.enemy, PD::CE, 0);
-  special_leapers(s.N, s.K, no, Fs, Ts, leap, visit);
+  special_leapers(s.N, s.K, no, Fs, Ts, visit);
   auto slide = [&](u64 targets, auto dtag) {
     constexpr int D = decltype(dtag)::value;
     while (targets) {
@@ -744,7 +641,7 @@ __device__ __forceinline__ void ref_for_each_special_pre(const Board& b, u64 Fs,
   leap(sh<PD::F>(push1 & PD::ROW_AFTER1) & e, 2 * PD::F, sh<2 * PD::F>(Fs) & Ts);
   leap(sh<PD::CW>(s.P & kNotA) & s.enemy, PD::CW, 0);
   leap(sh<PD::CE>(s.P & kNotH) & s.enemy, PD::CE, 0);
-  special_leapers(s.N, s.K, no, Fs, Ts, leap, visit);
+  special_leapers(s.N, s.K, no, Fs, Ts, visit);
   auto slide = [&](u64 targets, auto dtag) {
     constexpr int D = decltype(dtag)::value;
     while (targets) {

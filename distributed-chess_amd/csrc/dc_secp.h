@@ -793,10 +793,7 @@ constexpr int kGTabEntries = kGTabRows * 256;
 // 848 B/lane, 13 GB of HBM traffic per 262k-transaction launch).
 // W = 3: 4 entries (64 VGPRs), 43 windows x 2 halves; W = 4: 8 entries (128 VGPRs),
 // 33 windows.  G part: the byte table (32 mixed additions, no doublings).
-#ifndef DC_SECP_QW
-#define DC_SECP_QW 3
-#endif
-constexpr int kQWindow = DC_SECP_QW;
+constexpr int kQWindow = 3;
 
 // bits [pos, pos + len) of the 128-bit magnitude m (zero beyond bit 127)
 // (limbs picked by select: a runtime index would put m in scratch)

@@ -238,7 +238,7 @@ uint64_t or_fast_digest(const int8_t* cells, uint8_t stm) {
 
 // Legal-move counts of n quad-bitboard positions (bb[4*i..4*i+3], the device
 // Board layout; meta: castle rights | ep square << 4 | 0x400 when valid) --
-// the per-child recount of tools/fide_child_diag.py.
+// a host recount of boards taken from the device (tests/oracle_lib.py).
 void or_fast_count_quad(const uint64_t* bb, const uint8_t* stm, const uint16_t* meta, uint32_t n, int rules,
                         unsigned threads, uint32_t* out) {
   static const int8_t kind_of_code[8] = {-1, fastcpu::P, fastcpu::N, fastcpu::K, fastcpu::X,

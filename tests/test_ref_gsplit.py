@@ -1,5 +1,5 @@
 """CPU check of the REF final stage's target-side pawn correction (k_count3c,
-dc_ref.h ref_pawn_planes / ref_parent_split with DC_C2C_GCORR; restated in
+dc_ref.h ref_pawn_planes / ref_parent_split, round 5; restated in
 tools/ref_gsplit_proto.py).
 
 A quiet move of the side to move whose source is off the opponent's slider

@@ -1,7 +1,7 @@
 """c2c_group investigation: perft(5/6/7) of startpos
 through one build of libdchess.so (DCHESS_LIB), N runs each, printing the
 total and the per-root-move divide entries that differ from the golden.
-GPU tool:  TAG=soa DCHESS_LIB=.../lib_soa.so python tools/c2c_diag.py [runs]"""
+GPU tool:  TAG=name DCHESS_LIB=.../libdchess.so python tools/c2c_diag.py [runs]"""
 import os, sys, json
 sys.path.insert(0, os.path.join(os.getcwd(), "distributed-chess_amd"))
 import dchess

@@ -2,6 +2,7 @@
 §3.6): the FIDE final stage's grid from DC_DIAG_GRID (blocks), so a failing
 kernel can run on a chosen number of blocks without a CU mask.  The kernels'
 code is unchanged (tools/isa_norm_diff.py checks it)."""
+import re
 import sys
 
 p = sys.argv[1]
@@ -14,9 +15,10 @@ s = s.replace(anchor, "static u32 diag_grid() {\n  const char* e = getenv(\"DC_D
                       "  return e ? (u32)atoi(e) : kMaxGrid;\n}\n" + anchor, 1)
 # the REF final stage (k_count3c, dynamic groups: any grid is correct), if present
 for stm in ("1", "0"):
-    old = (f"    auto k = k_count3c<{stm}, kC3cCap, DC_C3C_MINW, W>;\n"
-           f"    hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)),")
-    if old in s:
+    old = re.search(rf"    auto k = k_count3c<{stm}, kC3cCap, \w+, W>;\n"
+                    r"    hipLaunchKernelGGL\(k, dim3\(resident_grid\(k, 256, kMaxGrid\)\),", s)
+    if old:
+        old = old.group(0)
         s = s.replace(old, old.replace("resident_grid(k, 256, kMaxGrid)", "resident_grid(k, 256, diag_grid3())"))
 if "diag_grid3()" in s:
     anchor = "template <class W>\nstatic hipError_t count3c_w("

@@ -14,7 +14,7 @@ assembly (.s) or on the disassembly of a built library's code objects:
       inactive lanes -- reported per VGPR.
 
 DESIGN.md section 3.6 records the outcome on the round-2 failing build
-(k_count3c<1, 6144, 4> of commit 3d8df08 with -DDC_C2C_SOA=1) and on the
+(k_count3c<1, 6144, 4> of commit 3d8df08 with its struct-of-arrays parents) and on the
 product; tests/test_spill_free.py runs it on the built library's kernels.
 
 usage: scratch_bounds_check.py FILE.s|LIB.so [kernel-substring ...]
