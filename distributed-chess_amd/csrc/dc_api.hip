@@ -234,6 +234,23 @@ struct dc_ctx {
   DBuf<uint8_t> front_st;  // k_front's look-back slots, a dc::FrontState (zeroed once; k_count3c re-zeroes them)
   DBuf<u32> front_spill;   // k_front's spill rows (items past one LDS window)
   uint8_t* front_st_zeroed = nullptr;
+  // k_front's transposition dedup (dc::FrontDedup, dc_perft.h): the hash table,
+  // each slot's owner index, the owners' totals, the per-board records, the state
+  DBuf<u64> fd_key, fd_total;
+  DBuf<u32> fd_owner, fd_rec_slot;
+  DBuf<uint16_t> fd_rec_flags;
+  DBuf<Board> fd_rec_board;
+  DBuf<dc::FrontDedupState> fd_state;
+  DBuf<dc::FrontDedup> fd_desc;    // the descriptor k_front reads (device copy of fd_desc_host)
+  dc::FrontDedup fd_desc_host{};
+  dc::FrontDedup* fd_desc_at = nullptr;  // where fd_desc_host was last uploaded
+  // the table and state that are known clean (zeroed, and every sequence that
+  // used them since was enqueued to its end: its k_front_fold frees what the
+  // run claimed); anything else gets a full clear before the next k_front
+  u64* fd_clean_key = nullptr;
+  dc::FrontDedupState* fd_clean_state = nullptr;
+  u64 front_hash_mask = ~0ull;     // ANDed into the board hashes (dc_test_front_hash_mask)
+  bool last_front_dedup = false;   // the last k_front enqueued deduplicated
   // transaction-signature check: staged strings / offsets / actions / turns,
   // and the G table (built on first use)
   DBuf<char> tx_text;
@@ -264,6 +281,14 @@ struct dc_ctx {
     top_words.release();
     front_st.release();
     front_spill.release();
+    fd_key.release();
+    fd_total.release();
+    fd_owner.release();
+    fd_rec_slot.release();
+    fd_rec_flags.release();
+    fd_rec_board.release();
+    fd_state.release();
+    fd_desc.release();
     move_words.release();
     dfs_stack.release();
     move_words64.release();
@@ -734,6 +759,37 @@ constexpr int kLiveDeclined = -1000;
 // one-launch front end (k_front), 0 when it took the legacy chain.
 extern "C" __attribute__((visibility("default"))) int dc_test_perft_last_front(const dc_ctx* c) {
   return c ? (int)c->last_front : -1;
+}
+
+// Test hook (not in the header): boards seen, owners and duplicates of the
+// context's last k_front run if it deduplicated its grandparents (zeros if not).
+extern "C" __attribute__((visibility("default"))) int dc_test_front_dedup_stats(dc_ctx* c, uint64_t out[3]) {
+  if (!c || !out) return DC_EINVAL;
+  out[0] = out[1] = out[2] = 0;
+  if (!c->last_front_dedup || !c->fd_state.p) return DC_SUCCESS;
+  if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return DC_EHIP;
+  dc::FrontDedupState st;
+  if (hipMemcpy(&st, c->fd_state.p, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return DC_EHIP;
+  for (int i = 0; i < 3; ++i) out[i] = st.stats[i];
+  return DC_SUCCESS;
+}
+
+// Test hook (not in the header): a mask ANDed into k_front's board hashes (all
+// ones by default), so a test can force hash collisions and check that each is
+// caught and the run declined.  k_front reads the mask from the FrontDedup
+// descriptor in device memory, which is rewritten here once queued work is
+// done; captured perft graphs stay valid and see the new mask on their next
+// replay (so a test can drive a decline inside a captured front-path graph).
+extern "C" __attribute__((visibility("default"))) int dc_test_front_hash_mask(dc_ctx* c, uint64_t mask) {
+  if (!c) return DC_EINVAL;
+  if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return DC_EHIP;
+  c->front_hash_mask = mask;
+  if (c->fd_desc.p && c->fd_desc_at == c->fd_desc.p) {  // (else the next front_enqueue uploads it)
+    c->fd_desc_host.hash_mask = mask;
+    if (hipMemcpy(c->fd_desc.p, &c->fd_desc_host, sizeof(c->fd_desc_host), hipMemcpyHostToDevice) != hipSuccess)
+      return DC_EHIP;
+  }
+  return DC_SUCCESS;
 }
 
 // Test hook (not in the header): the state hash's pre-pass budget in bytes, so
@@ -1713,9 +1769,21 @@ static bool front_eligible(uint32_t rules, uint32_t depth, uint32_t split_depth,
   return n_shards == 1 || (S == 3 && !shard_contiguous());
 }
 
-// k_front's sequence: the root upload (stage_root), k_front, k_count3c.
-static int front_enqueue(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t shard, uint32_t n_shards,
-                         bool stage_root) {
+// Which k_front shapes deduplicate their grandparents (DESIGN.md section 3.9:
+// decided by measurement).  DC_FRONT_DEDUP (A/B build) is a mask: 1 perft(7)
+// unsharded, 2 perft(7) shards, 4 perft(6) unsharded, 8 perft(6) shards.
+static u32 front_dedup_shapes() {
+  static const u32 m = [] {
+    const char* e = dc::ab_env("DC_FRONT_DEDUP");
+    return e ? (u32)std::strtoul(e, nullptr, 0) : 1u;
+  }();
+  return m;
+}
+
+// k_front's sequence: the root upload (stage_root), k_front, k_count3c (and,
+// where the grandparents are deduplicated, k_front_fold).
+static int front_enqueue_seq(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t shard, uint32_t n_shards,
+                             bool stage_root) {
   if (!c->res_host) HIP_TRY(hipHostMalloc((void**)&c->res_host, sizeof(dc::PerftResult)));
   if (!c->root_host) {
     HIP_TRY(hipHostMalloc((void**)&c->root_host, sizeof(*c->root_host)));
@@ -1738,6 +1806,37 @@ static int front_enqueue(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t 
   if (e != DC_SUCCESS) return e;
   HIP_TRY(c->move_words.ensure(cap_w));
   HIP_TRY(c->front_spill.ensure(dc::front_spill_words()));
+  const bool dedup = (front_dedup_shapes() >> ((depth == 7 ? 0 : 2) + (n_shards > 1 ? 1 : 0))) & 1;
+  dc::FrontDedup dd{};
+  if (dedup) {
+    constexpr u32 kSlots = 2 * (u32)dc::kMoveWordNodesMax;  // at most cap_b owners: half full
+    static_assert(kSlots <= 1u << 21, "a record's slot word keeps the slot in 21 bits");
+    HIP_TRY(c->fd_key.ensure(kSlots));
+    HIP_TRY(c->fd_owner.ensure(kSlots));
+    HIP_TRY(c->fd_total.ensure((size_t)cap_b + 256));  // (+ a group's span: k_count3c's flush)
+    HIP_TRY(c->fd_rec_slot.ensure(cap_b));
+    HIP_TRY(c->fd_rec_flags.ensure(cap_b));
+    HIP_TRY(c->fd_rec_board.ensure(cap_b));
+    HIP_TRY(c->fd_state.ensure(1));
+    if (c->fd_clean_key != c->fd_key.p || c->fd_clean_state != c->fd_state.p) {
+      HIP_TRY(hipMemsetAsync(c->fd_key.p, 0, (size_t)kSlots * sizeof(u64), c->stream));
+      HIP_TRY(hipMemsetAsync(c->fd_state.p, 0, sizeof(dc::FrontDedupState), c->stream));
+    }
+    // not clean again until the sequence below is enqueued to its end
+    c->fd_clean_key = nullptr;
+    c->fd_clean_state = nullptr;
+    dd = dc::FrontDedup{c->fd_key.p,      c->fd_owner.p,     c->fd_total.p, c->fd_rec_slot.p, c->fd_rec_flags.p,
+                        c->fd_rec_board.p, c->fd_state.p,     c->front_hash_mask, kSlots - 1, cap_b};
+  }
+  if (dedup) {
+    HIP_TRY(c->fd_desc.ensure(1));
+    if (c->fd_desc_at != c->fd_desc.p || std::memcmp(&c->fd_desc_host, &dd, sizeof(dd)) != 0) {
+      c->fd_desc_host = dd;  // (the copy's source outlives the call)
+      HIP_TRY(hipMemcpyAsync(c->fd_desc.p, &c->fd_desc_host, sizeof(dd), hipMemcpyHostToDevice, c->stream));
+      c->fd_desc_at = c->fd_desc.p;
+    }
+  }
+  c->last_front_dedup = dedup;
   if (stage_root) {
     e = write_root_host(c, pos, 1);
     if (e == DC_SUCCESS) e = upload_roots(c, 1, false);
@@ -1746,15 +1845,37 @@ static int front_enqueue(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t 
   dc::Range* rng = c->rng.p + 8;  // [8] the grandparents, [9] the move words
   HIP_TRY(c->timed("front", 0, [&] {
     return dc::launch_front(c->stream, pos->stm, depth, c->root.p, shard, n_shards, c->nodes[0].p, c->tags[0].p,
-                            cap_b, c->move_words.p, cap_w, c->res.p, rng, fst, c->front_spill.p);
+                            cap_b, c->move_words.p, cap_w, c->res.p, rng, fst, c->front_spill.p,
+                            dedup ? c->fd_desc.p : nullptr);
   }));
   c->last_final = "count2";
   const int stm_g = pos->stm ^ (int)((depth - 3) & 1);  // the grandparents are ply depth - 3
   HIP_TRY(c->timed("count2", 0, [&] {
     return dc::launch_count3c(c->stream, stm_g, c->nodes[0].p, c->tags[0].p, rng, rng + 1, c->move_words.p,
-                              c->res.p, nullptr, fst);
+                              c->res.p, nullptr, fst, dedup ? dd.gp_total : nullptr);
   }));
+  if (dedup) {
+    HIP_TRY(c->timed("fold", 0, [&] { return dc::launch_front_fold(c->stream, dd, c->nodes[0].p, rng, c->res.p); }));
+    c->fd_clean_key = c->fd_key.p;
+    c->fd_clean_state = c->fd_state.p;
+  }
   return DC_SUCCESS;
+}
+
+// A deduplicating sequence that failed part-way leaves the table unclean
+// (fd_clean_*): the next front_enqueue clears it in full, but a captured graph
+// would replay without that clear and decline run after run, so the captured
+// graphs are dropped with it.
+static int front_enqueue(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t shard, uint32_t n_shards,
+                         bool stage_root) {
+  const int e = front_enqueue_seq(c, pos, depth, shard, n_shards, stage_root);
+  if (e != DC_SUCCESS && c->fd_key.p && c->fd_clean_key != c->fd_key.p) {
+    for (hipGraphExec_t* ge : {&c->pgraph, &c->rgraph, &c->rgraph_batch}) {
+      if (*ge) (void)hipGraphExecDestroy(*ge);
+      *ge = nullptr;
+    }
+  }
+  return e;
 }
 
 int perft_enqueue(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,

@@ -111,9 +111,12 @@ struct FrontState;
 // cleared for the next run.  (Round 6 also tried the run's result record
 // written by the last block to finish instead of k_copy_result: a done
 // counter and a device fence per block cost more than the launch.)
+// gp_total != nullptr (after a deduplicating launch_front): every grandparent's
+// leaves are added into gp_total[its index] instead of res->divide[its tag]
+// (tags is not read); launch_front_fold then makes the divide.
 hipError_t launch_count3c(hipStream_t st, int stm_g, const Board* nodes, const uint16_t* tags, const Range* rng,
                           const Range* rng_ch, const u32* mw, PerftResult* res, u32* counter = nullptr,
-                          FrontState* fst = nullptr);
+                          FrontState* fst = nullptr, u64* gp_total = nullptr);
 // The same with u64 words {grandparent index << 12 | f | t << 6} (no 2^20
 // grandparent limit): REF perft(8)'s final stage below ply 5.
 hipError_t launch_level_moves(hipStream_t st, int stm, const Board* nodes, const Range* rng, u64 n_bound,
@@ -136,7 +139,7 @@ hipError_t launch_wide_slice(hipStream_t st, const Range* lvl, const u64* chunk_
 // state block (the items' look-back slots) must be zero before the first
 // launch; the launch_count3c given it clears them again.  A top past the
 // kernel's LDS bounds (more than 128 root moves or 2,048 ply-2 nodes), an item
-// of more than 1,024 boards or a level past its capacity sets overflow and
+// of more than 2,048 boards or a level past its capacity sets overflow and
 // front_declined.
 constexpr u32 kFrontItemsMax = 1u << 16;
 struct FrontState {
@@ -144,12 +147,61 @@ struct FrontState {
   u64 agg[kFrontItemsMax];
   u64 incl[kFrontItemsMax];
 };
+// Transposition dedup of the grandparents (dd != nullptr; DESIGN.md section
+// 3.9): under REF rules a subtree's leaf count depends only on the four
+// bitboards (the side to move is the ply's), so a board reached by several
+// move orders is written, expanded and counted once.
+//  * key[slots] (slots a power of two): an open-addressing table of 64-bit
+//    board hashes, 0 = free, claimed with a relaxed atomicCAS and linear
+//    probing (at most kFrontProbeMax probes, then the run is declined).  The
+//    claiming board is the hash's *owner*; only owners are emitted.
+//  * rec_slot / rec_flags / rec_board[cap_rec]: one record per board seen
+//    (its table slot -- the low 21 bits; a kept owner's index within its item
+//    above them --, kFrontRec* | root tag, and -- duplicates only -- the
+//    board itself), reserved with one atomicAdd per item on st->n_rec.
+//  * owner_index[slots]: the owner's index in `out`, written once the item's
+//    offsets are known; gp_total[cap_b]: the leaves below owner i, zeroed by
+//    k_front and added to by launch_count3c(gp_total).
+//  * launch_front_fold, after launch_count3c: divide[tag] += gp_total[owner]
+//    for every record.  A duplicate is first compared with its owner's board
+//    in `out`, all four words: a mismatch (a hash collision, or a table not
+//    clean when the run began) sets overflow and front_declined, never a
+//    count.  It then frees the table slots the run claimed and resets
+//    n_rec, whether or not the run was declined.
+// All of it must be zero before the first launch; a sequence that did not run
+// to its end (a failed launch) needs the table and the state zeroed again.
+// hash_mask is ANDed into every hash (all ones; a test narrows it to force
+// collisions).
+constexpr u32 kFrontProbeMax = 32;
+constexpr uint16_t kFrontRecOwner = 0x8000, kFrontRecChildless = 0x4000;  // (the low byte: the root tag)
+struct FrontDedupState {
+  u32 n_rec;     // records reserved by the run (may pass cap_rec: the run is declined)
+  u32 done;      // fold blocks finished (the last one resets n_rec and done)
+  u64 stats[3];  // boards seen, owners, duplicates of the last run (dc_test_front_dedup_stats)
+};
+struct FrontDedup {
+  u64* key;
+  u32* owner_index;
+  u64* gp_total;
+  u32* rec_slot;
+  uint16_t* rec_flags;
+  Board* rec_board;
+  FrontDedupState* st;
+  u64 hash_mask;
+  u32 slot_mask;  // slots - 1
+  u32 cap_rec;
+};
 // spill (front_spill_words() u32, or null): per-item rows for the words of
 // items past one LDS window (no second walk).
 u64 front_spill_words();
 hipError_t launch_front(hipStream_t st, int stm0, u32 depth, const Board* root, u32 shard, u32 n_shards, Board* out,
                         uint16_t* out_tags, u32 cap_b, u32* mw, u64 cap_w, PerftResult* res, Range* rng_out,
-                        FrontState* fst, u32* spill);
+                        FrontState* fst, u32* spill, const FrontDedup* dd = nullptr);
+// (dd: a FrontDedup in device memory -- k_front reads its fields where it uses
+// them; passed by value, its ten fields sat in registers for the whole kernel)
+// rng_out: launch_front's (rng_out[0] = the owners' Range).
+hipError_t launch_front_fold(hipStream_t st, const FrontDedup& dd, const Board* out, const Range* rng_out,
+                             PerftResult* res);
 
 // K4 (REF): per-lane DFS over L plies below the frontier level `rng` (1 <= L <= 3),
 // each level-L node bulk-counted over the last two plies (perft depth = frontier

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "dc_common.h"
 #include "dc_perft.h"
@@ -755,9 +756,18 @@ __global__ __launch_bounds__(256) void k_level_moves(const Board* __restrict__ n
 //    item's offsets come from a decoupled look-back over the earlier items'
 //    published (boards, words) -- no same-address atomics (a first version
 //    took both from two global cursors: 768 blocks queued on them for up to
-//    ~15 us) -- so both levels come out in the canonical order of the legacy
-//    chain.  The item's words are walked into an LDS window (board index
-//    relative to the item) before the look-back and rebased when stored.
+//    ~15 us) -- so both levels come out in item order, the words sorted by
+//    their board's index.  The item's words are walked into an LDS window
+//    (board index relative to the item) before the look-back and rebased when
+//    stored.
+//  * DEDUP (dc_perft.h, FrontDedup): every board of an item is hashed and
+//    inserted into the context's table; only the boards that claim their hash
+//    (owners) and have a move are kept -- compacted in LDS before the word
+//    offsets are scanned -- so a board reached by several move orders is
+//    written and counted once.  Which of them owns the hash depends on which
+//    block's atomicCAS lands first, so the order of the boards written varies
+//    from run to run; every result is a sum over them.  The duplicates leave
+//    a record each, which k_front_fold checks and adds up after k_count3c.
 //  * Every serial walk is split over the four class groups of
 //    ref_group_moves (a lane walks a quarter of a position's moves).  Group g
 //    is taken by waves 4g .. 4g + 3, which sit on the four SIMDs, so each SIMD
@@ -776,6 +786,16 @@ constexpr u32 kFrontWin = 28672;       // move words of one LDS window (112 KB: 
                                        // hold 12k-32k words)
 constexpr u32 kFrontSpillItems = 1024; // items with a spill row for a second window
 constexpr u32 kFrontChunk = 5;         // consecutive ply-3 nodes per chunk of an item
+
+// DEDUP: the 64-bit key of a board (the table keeps 0 for a free slot)
+__device__ __forceinline__ u64 front_hash(const Board& b) {
+  u64 x = b.b0 * 0x9E3779B97F4A7C15ull;
+  x = ((x ^ (x >> 32)) + b.b1) * 0xBF58476D1CE4E5B9ull;
+  x = ((x ^ (x >> 29)) + b.b2) * 0x94D049BB133111EBull;
+  x = ((x ^ (x >> 32)) + b.b3) * 0xD6E8FEB86659FD93ull;
+  x = (x ^ (x >> 32)) * 0xBF58476D1CE4E5B9ull;
+  return x ^ (x >> 29);
+}
 
 #ifdef DC_AB_KNOBS
 // A/B build: k_front's timeline (wall clock, 100 MHz) per block:
@@ -818,7 +838,8 @@ struct FrontShared {
   uint16_t m1[kFrontPly1Max];
   u32 gc[4][kFrontP3Max];    // per-group move counts (ply 2, selection, ply 4)
   u32 noff[kFrontP3Max];     // per-node move offsets (ply 2, ply 4)
-  u32 slot4[kFrontBoardsMax];      // E = 1: an item's ply-4 moves (ply-3 node << 12 | f | t << 6)
+  u32 slot4[kFrontBoardsMax];      // E = 1: an item's ply-4 moves (ply-3 node << 12 | f | t << 6);
+                                   // DEDUP, E = 0: the kept ply-3 nodes (node << 12)
   u32 woff[kFrontBoardsMax];       // per-board word offsets
   u64 red[kFrontWaves][3];
   u64 tot[3];
@@ -932,12 +953,18 @@ __device__ __forceinline__ void front_lookback(FrontShared& sh, FrontState* st, 
 // puts the words past the first in its spill row during the one walk and
 // copies them to their place after the look-back (a second walk of the item
 // made the ~3 % of startpos perft(7) items past one window the last blocks).
-template <int S0, int E>
-__global__ __launch_bounds__(kFrontThreads) void k_front(const Board* __restrict__ root_p, u32 shard, u32 n_shards,
+// amdgpu_num_vgpr(60): the attribute counts the unified register file of
+// gfx90a and later in pairs, so this caps a wave at 120 registers.  A
+// 1,024-thread block is four waves per SIMD: at 128 each it would take every
+// register of its CU and could not start beside another kernel's waves (the
+// plain kernel needs 108-114, the deduplicating one was allocated 118-125).
+template <int S0, int E, bool DEDUP = false>
+__global__ __launch_bounds__(kFrontThreads) __attribute__((amdgpu_num_vgpr(60))) void k_front(const Board* __restrict__ root_p, u32 shard, u32 n_shards,
                                                          Board* __restrict__ out, uint16_t* __restrict__ out_tags,
                                                          u32 cap_b, u32* __restrict__ mw, u64 cap_w,
                                                          PerftResult* __restrict__ res, Range* __restrict__ rng_out,
-                                                         FrontState* __restrict__ st, u32* __restrict__ spill) {
+                                                         FrontState* __restrict__ st, u32* __restrict__ spill,
+                                                         const FrontDedup* __restrict__ dd) {
   constexpr int S1 = S0 ^ 1;       // side to move at ply 1 (and ply 3)
   constexpr int SF = E ? S0 : S1;  // side to move at the boards written
   constexpr u32 NT = kFrontThreads, NW = kFrontWaves;
@@ -949,6 +976,8 @@ __global__ __launch_bounds__(kFrontThreads) void k_front(const Board* __restrict
   if (blockIdx.x == 0) {
     static_assert(sizeof(PerftResult) % 8 == 0, "PerftResult is cleared in u64 words");
     for (u32 k = t; k < sizeof(PerftResult) / 8; k += NT) reinterpret_cast<u64*>(res)[k] = 0;
+    if constexpr (DEDUP)
+      if (t < 3) dd->st->stats[t] = 0;  // (k_front_fold counts the run's records)
   }
   const Board root = root_p[0];
   u32 n1 = 0, n2 = 0, n3 = 0;
@@ -1117,6 +1146,9 @@ __global__ __launch_bounds__(kFrontThreads) void k_front(const Board* __restrict
       }
       __syncthreads();
       if (it == blockIdx.x) DC_FRONT_STAMP(7);
+    } else if constexpr (DEDUP) {
+      if (t < np3) sh.slot4[t] = t << 12;
+      __syncthreads();
     }
     if (bad) nbd = 0;
     auto board_at = [&](u32 k) -> Board {
@@ -1125,15 +1157,102 @@ __global__ __launch_bounds__(kFrontThreads) void k_front(const Board* __restrict
         Board b = sh.b3[e >> 12];
         ref_make(b, (int)(e & 63), (int)((e >> 6) & 63));
         return b;
+      } else if constexpr (DEDUP) {
+        return sh.b3[sh.slot4[k] >> 12];
       } else {
         return sh.b3[k];
       }
     };
+    auto tag_at = [&](u32 k) -> uint16_t {
+      if constexpr (E == 1 || DEDUP) return sh.t3[sh.slot4[k] >> 12];
+      else return sh.t3[k];
+    };
     // -- pass 1: word counts per (group, board)
     for (u32 k = qlane; k < nbd; k += 256) sh.gw[grp][k] = (uint16_t)front_group_count<SF>(grp, board_at(k));
     __syncthreads();
-    const u32 seg = (nbd + NT - 1) / NT, a = min(nbd, t * seg), z = min(nbd, a + seg);
     auto wcount = [&](u32 k) -> u32 { return (u32)sh.gw[0][k] + sh.gw[1][k] + sh.gw[2][k] + sh.gw[3][k]; };
+    // -- DEDUP: insert the item's boards; keep the owners that have a move.
+    //    A thread takes up to two consecutive boards [d_a, ...): bit i of d_em
+    //    = board d_a + i is kept, as board d_first + (kept ones before it).
+    //    (Nothing per thread stays live over the walk and the look-back: a
+    //    kept board's index in the item goes into the upper bits of its
+    //    record's slot word and is read back.  The kernel must stay at 120
+    //    VGPRs or fewer, so that a block still fits a CU beside another
+    //    kernel's waves.)
+    [[maybe_unused]] u32 d_roff = 0, nbd0 = 0;
+    if constexpr (DEDUP) {
+      static_assert(kFrontBoardsMax <= 2 * NT, "two boards per thread");
+      nbd0 = __builtin_amdgcn_readfirstlane(nbd);
+      u32 d_a, d_em = 0, d_first;
+      // the item's records: one atomicAdd (nothing waits on it but this item)
+      if (t == 0) sh.jm = nbd0 ? atomicAdd(&dd->st->n_rec, nbd0) : 0u;
+      __syncthreads();
+      d_roff = __builtin_amdgcn_readfirstlane(sh.jm);
+      // (else: no insert, the run is declined; made scalar, so the branch on it is no VCC branch)
+      const bool rfit = __builtin_amdgcn_readfirstlane((u32)((u64)d_roff + nbd0 <= dd->cap_rec)) != 0;
+      const u32 seg0 = (nbd0 + NT - 1) / NT;
+      d_a = min(nbd0, t * seg0);
+      const u32 z0 = min(nbd0, d_a + seg0);
+      bool fail = false;
+      if (rfit)
+#pragma unroll 1
+        for (u32 k = d_a; k < z0; ++k) {
+          const Board b = board_at(k);
+          const u32 wc = wcount(k);
+          u64 h = front_hash(b) & dd->hash_mask;
+          if (h == 0) h = 1;
+          u32 s = (u32)h & dd->slot_mask;
+          u32 r = 2;  // 0 owner, 1 duplicate of the slot's owner (checked by the fold), 2 no slot within the bound
+#pragma unroll 1
+          for (u32 pr = 0; pr < kFrontProbeMax; ++pr) {
+            u64 cur = __hip_atomic_load(&dd->key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == 0 && __hip_atomic_compare_exchange_strong(&dd->key[s], &cur, h, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_AGENT)) {
+              r = 0;
+              break;
+            }
+            if (cur == h) {
+              r = 1;
+              break;
+            }
+            s = (s + 1) & dd->slot_mask;
+          }
+          dd->rec_slot[d_roff + k] = s;
+          dd->rec_flags[d_roff + k] = (uint16_t)(tag_at(k) | (r == 0 ? kFrontRecOwner : 0) |
+                                                (wc == 0 || r == 2 ? kFrontRecChildless : 0));
+          if (r == 1 && wc) store_board(dd->rec_board, d_roff + k, b);
+          fail |= r == 2;
+          if (r == 0 && wc) d_em |= 1u << (k - d_a);
+        }
+      bad = __syncthreads_or(!rfit || fail) || bad;  // block-uniform
+      if (bad) d_em = 0;
+      u32 n_own;
+      d_first = block_excl_scan32<NW>((u32)__popc(d_em), sh.wsum, &n_own);
+      // compact slot4 and the counts through the (still free) word window
+      u32* tmp4 = sh.slotw;
+      uint16_t* tmpg = reinterpret_cast<uint16_t*>(sh.slotw + kFrontBoardsMax);
+      static_assert(3 * kFrontBoardsMax <= kFrontWin, "the window holds the compaction");
+      {
+        static_assert(kFrontBoardsMax <= 1u << 11, "the item index fits above the 21-bit slot");
+        u32 j = d_first;
+#pragma unroll 1
+        for (u32 k = d_a; k < z0; ++k)
+          if ((d_em >> (k - d_a)) & 1) {
+            dd->rec_slot[d_roff + k] |= j << 21;
+            tmp4[j] = sh.slot4[k];
+            for (u32 g = 0; g < 4; ++g) tmpg[g * kFrontBoardsMax + j] = sh.gw[g][k];
+            ++j;
+          }
+      }
+      __syncthreads();
+      for (u32 k = t; k < n_own; k += NT) {
+        sh.slot4[k] = tmp4[k];
+        for (u32 g = 0; g < 4; ++g) sh.gw[g][k] = tmpg[g * kFrontBoardsMax + k];
+      }
+      __syncthreads();
+      nbd = n_own;
+    }
+    const u32 seg = (nbd + NT - 1) / NT, a = min(nbd, t * seg), z = min(nbd, a + seg);
     u32 s = 0;
     for (u32 k = a; k < z; ++k) s += wcount(k);
     u32 nw;
@@ -1186,8 +1305,23 @@ __global__ __launch_bounds__(kFrontThreads) void k_front(const Board* __restrict
     if (fits)
       for (u32 k = t; k < nbd; k += NT) {
         store_board(out, base_b + k, board_at(k));
-        out_tags[base_b + k] = E == 1 ? sh.t3[sh.slot4[k] >> 12] : sh.t3[k];
+        out_tags[base_b + k] = tag_at(k);
       }
+    if constexpr (DEDUP) {  // where the fold finds each owner's total
+      if (fits) {
+        for (u32 k = t; k < nbd; k += NT) dd->gp_total[base_b + k] = 0;
+#pragma unroll 1
+        // (record k was written by another thread of the block, thread k / seg0;
+        // the block barriers since then order its global writes before these reads)
+        for (u32 k = t; k < nbd0; k += NT) {
+          const u32 fl = dd->rec_flags[d_roff + k];
+          if ((fl & kFrontRecOwner) && !(fl & kFrontRecChildless)) {
+            const u32 sw = dd->rec_slot[d_roff + k];
+            dd->owner_index[sw & dd->slot_mask] = (u32)base_b + (sw >> 21);
+          }
+        }
+      }
+    }
 #ifdef DC_AB_KNOBS
     if (it == blockIdx.x && t == 0 && blockIdx.x < kFrontTraceBlocks) {
       g_front_trace[blockIdx.x * kFrontTraceWords + 13] = nw;
@@ -2057,7 +2191,14 @@ constexpr u32 kMoveWordNodes = 1u << 20;  // grandparent index field of a move w
 // speculative bound) is flagged by the scan that sizes its children
 // (k_chunk_scan's guard): the children's Range is empty and
 // the host reruns in exact mode, which takes the k_level_write path.
-template <int STM_G, u32 CAP, int MINW = 4, class W = u32>
+// DEDUP (after a deduplicating k_front): `divide` is gp_total, one u64 per
+// grandparent, and `tags` is not read.  The words are sorted by grandparent and
+// every grandparent written has a word, so a group's 256 words span fewer than
+// 256 consecutive grandparents: c2c_group gets the grandparent's index
+// relative to the group's first as its tag, and the block's histogram is
+// added into gp_total and cleared after every group (a grandparent's words
+// can straddle two groups).  k_front_fold turns gp_total into the divide.
+template <int STM_G, u32 CAP, int MINW = 4, class W = u32, bool DEDUP = false>
 __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__ nodes, const uint16_t* __restrict__ tags,
                                                  const Range* __restrict__ rng, const Range* __restrict__ rng_ch,
                                                  const W* __restrict__ mw, u64* __restrict__ divide,
@@ -2098,21 +2239,121 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
     const bool valid = ot < kGroup && i < total;
     Board ch{0, 0, 0, 0};
     u32 tag = 0;
+    [[maybe_unused]] u32 g_first = 0;  // DEDUP: the group's first grandparent (block-uniform)
+    if constexpr (DEDUP) g_first = (u32)(mw[s] >> 12);
     if (valid) {
       const W e = mw[i];
       const u64 g = lo + (u64)(e >> 12);
       ch = load_board(nodes, g);
-      tag = tags[g];
+      if constexpr (DEDUP) tag = (u32)(e >> 12) - g_first;
+      else tag = tags[g];
       const u32 mv = (u32)e;
       ref_make(ch, (int)(mv & 63), (int)((mv >> 6) & 63));
     }
     c2c_group<1 - STM_G, CAP>(sh, valid, ch, tag, divide, wave);
     // (c2c_group ended with a barrier: every thread is past its read of grp's state)
+    if constexpr (DEDUP) {
+      // (the next group's first add into hist comes after c2c_group's first barrier)
+      if (ot < 256) {
+        const u64 v = sh.hist[ot];
+        if (v) {
+          atomicAdd((unsigned long long*)(divide + lo + g_first + ot), (unsigned long long)v);
+          sh.hist[ot] = 0;
+        }
+      }
+    }
     if (t0) sh.next = gridDim.x + atomicAdd(next_group, 1u);
     __syncthreads();
     grp = sh.next;
   }
-  tag_hist_flush(sh.hist, divide, otid(wave));
+  if constexpr (!DEDUP) tag_hist_flush(sh.hist, divide, otid(wave));
+}
+
+// After k_front<.., DEDUP> and k_count3c<.., DEDUP>: the run's divide from
+// gp_total, one record per board k_front saw (dc_perft.h, FrontDedup).  An
+// owner adds its own total under its root tag; a duplicate adds its owner's,
+// after its board compared equal to the owner's in `out` -- else (a hash
+// collision, or a slot left over from a sequence that did not finish) the run
+// is flagged overflow + front_declined like any run k_front declines, and the
+// host reruns on the legacy chain.  Every claimed table slot is freed here,
+// declined run or not; the last block to finish resets the record cursor.
+__global__ __launch_bounds__(256) void k_front_fold(const FrontDedup dd, const Board* __restrict__ out,
+                                                    const Range* __restrict__ rng_out, PerftResult* __restrict__ res) {
+  __shared__ u64 hist[256];
+  __shared__ u32 cnt[2];
+  tag_hist_init(hist);
+  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+  const u32 n_res = dd.st->n_rec;
+  const u32 n = min(n_res, dd.cap_rec);  // (past cap_rec: k_front inserted nothing for those and declined)
+  const u64 tb = rng_out[0].hi - rng_out[0].lo;  // owners written (0: the run was declined)
+  u32 n_own = 0, n_dup = 0;
+  bool mism = false;
+  // Four records per thread and pass, each stage's loads issued together: a
+  // record is a chain of three dependent, scattered loads (record -> owner
+  // index -> total / board), and one record per pass left the kernel waiting
+  // on that chain pass after pass.
+  constexpr u32 R = 4;
+  for (u32 base = blockIdx.x * (256 * R); base < n; base += gridDim.x * (256 * R)) {  // block-uniform
+    u32 fl[R], s[R], oi[R];
+    u64 v[R];
+    bool live[R], cmp[R];
+#pragma unroll
+    for (u32 r = 0; r < R; ++r) {
+      const u32 i = base + r * 256 + threadIdx.x;
+      live[r] = i < n;
+      fl[r] = live[r] ? dd.rec_flags[i] : (u32)kFrontRecChildless;
+      s[r] = live[r] ? dd.rec_slot[i] & dd.slot_mask : 0u;
+    }
+#pragma unroll
+    for (u32 r = 0; r < R; ++r) {
+      oi[r] = fl[r] & kFrontRecChildless ? 0u : dd.owner_index[s[r]];
+      const bool hit = !(fl[r] & kFrontRecChildless) && oi[r] < tb;
+      mism |= !(fl[r] & kFrontRecChildless) && oi[r] >= tb;
+      cmp[r] = hit && !(fl[r] & kFrontRecOwner);
+      live[r] = live[r] && hit;  // from here on: the record adds a total
+    }
+    Board ra[R], rb[R];
+#pragma unroll
+    for (u32 r = 0; r < R; ++r) {
+      v[r] = live[r] ? dd.gp_total[oi[r]] : 0ull;
+      if (cmp[r]) {
+        ra[r] = load_board(dd.rec_board, base + r * 256 + threadIdx.x);
+        rb[r] = load_board(out, oi[r]);
+      }
+    }
+#pragma unroll
+    for (u32 r = 0; r < R; ++r) {
+      if (cmp[r] && !(ra[r].b0 == rb[r].b0 && ra[r].b1 == rb[r].b1 && ra[r].b2 == rb[r].b2 && ra[r].b3 == rb[r].b3)) {
+        mism = true;
+        v[r] = 0;
+      }
+      const bool in = base + r * 256 + threadIdx.x < n;
+      if (in && (fl[r] & kFrontRecOwner)) {
+        dd.key[s[r]] = 0;
+        ++n_own;
+      } else if (in) {
+        ++n_dup;
+      }
+      tag_hist_add(hist, fl[r] & 255u, v[r], live[r]);
+    }
+  }
+  if (mism) {
+    res->overflow = 1;
+    res->front_declined = 1;
+  }
+  if (n_own) atomicAdd(&cnt[0], n_own);
+  if (n_dup) atomicAdd(&cnt[1], n_dup);
+  tag_hist_flush(hist, res->divide);  // (starts with a barrier)
+  if (threadIdx.x == 0) {
+    if (cnt[0]) atomicAdd((unsigned long long*)&dd.st->stats[1], (unsigned long long)cnt[0]);
+    if (cnt[1]) atomicAdd((unsigned long long*)&dd.st->stats[2], (unsigned long long)cnt[1]);
+    // every block has read n_rec before its own count here
+    if (atomicAdd(&dd.st->done, 1u) == gridDim.x - 1) {
+      dd.st->stats[0] = n_res;
+      dd.st->n_rec = 0;
+      dd.st->done = 0;
+    }
+  }
 }
 
 // ------------------------------------------------- K4: per-lane DFS (REF)
@@ -2521,8 +2762,23 @@ constexpr u32 kC3cCap = kC2cCap;
 constexpr int kC3cMinWaves = 4;
 template <class W>
 static hipError_t count3c_w(hipStream_t st, int stm_g, const Board* nodes, const uint16_t* tags, const Range* rng,
-                            const Range* rng_ch, const W* mw, PerftResult* res, u32* counter, FrontState* fst = nullptr) {
+                            const Range* rng_ch, const W* mw, PerftResult* res, u32* counter, FrontState* fst = nullptr,
+                            u64* gp_total = nullptr) {
   u32* next = counter ? counter : &res->next_chunk;
+  if constexpr (std::is_same_v<W, u32>) {
+    if (gp_total) {  // after a deduplicating k_front: per-grandparent totals (tags unused)
+      if (stm_g) {
+        auto k = k_count3c<1, kC3cCap, kC3cMinWaves, W, true>;
+        hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
+                           gp_total, next, fst);
+      } else {
+        auto k = k_count3c<0, kC3cCap, kC3cMinWaves, W, true>;
+        hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
+                           gp_total, next, fst);
+      }
+      return hipGetLastError();
+    }
+  }
   if (stm_g) {
     auto k = k_count3c<1, kC3cCap, kC3cMinWaves, W>;
     hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
@@ -2535,8 +2791,9 @@ static hipError_t count3c_w(hipStream_t st, int stm_g, const Board* nodes, const
   return hipGetLastError();
 }
 hipError_t launch_count3c(hipStream_t st, int stm_g, const Board* nodes, const uint16_t* tags, const Range* rng,
-                          const Range* rng_ch, const u32* mw, PerftResult* res, u32* counter, FrontState* fst) {
-  return count3c_w(st, stm_g, nodes, tags, rng, rng_ch, mw, res, counter, fst);
+                          const Range* rng_ch, const u32* mw, PerftResult* res, u32* counter, FrontState* fst,
+                          u64* gp_total) {
+  return count3c_w(st, stm_g, nodes, tags, rng, rng_ch, mw, res, counter, fst, gp_total);
 }
 hipError_t launch_count3c(hipStream_t st, int stm_g, const Board* nodes, const uint16_t* tags, const Range* rng,
                           const Range* rng_ch, const u64* mw, PerftResult* res, u32* counter) {
@@ -2556,24 +2813,45 @@ u64 front_spill_words() { return (u64)kFrontSpillItems * kFrontWin; }
 
 hipError_t launch_front(hipStream_t st, int stm0, u32 depth, const Board* root, u32 shard, u32 n_shards, Board* out,
                         uint16_t* out_tags, u32 cap_b, u32* mw, u64 cap_w, PerftResult* res, Range* rng_out,
-                        FrontState* fst, u32* spill) {
+                        FrontState* fst, u32* spill, const FrontDedup* dd) {
   if (depth != 6 && depth != 7) return hipErrorInvalidValue;
   // one pass of the resident grid: every block does the top once
-#define DC_FRONT(S, E)                                                                                        \
+#define DC_FRONT(S, E, D)                                                                                     \
   do {                                                                                                        \
-    auto k_ = k_front<S, E>;                                                                                  \
+    auto k_ = k_front<S, E, D>;                                                                               \
     hipLaunchKernelGGL(k_, dim3(resident_grid(k_, kFrontThreads, kMaxGrid)), dim3(kFrontThreads), 0, st, root,    \
                        shard, n_shards,                                                                       \
-                       out, out_tags, cap_b, mw, cap_w, res, rng_out, fst, spill);                            \
+                       out, out_tags, cap_b, mw, cap_w, res, rng_out, fst, spill, dd);                        \
+  } while (0)
+#define DC_FRONT_D(S, E)          \
+  do {                            \
+    if (dd) DC_FRONT(S, E, true); \
+    else DC_FRONT(S, E, false);   \
   } while (0)
   if (depth == 7) {
-    if (stm0) DC_FRONT(1, 1);
-    else DC_FRONT(0, 1);
+    if (stm0) DC_FRONT_D(1, 1);
+    else DC_FRONT_D(0, 1);
   } else {
-    if (stm0) DC_FRONT(1, 0);
-    else DC_FRONT(0, 0);
+    // perft(6) measured slower with the dedup: its
+    // instantiations exist only in the A/B build (DC_FRONT_DEDUP)
+#ifdef DC_AB_KNOBS
+    if (stm0) DC_FRONT_D(1, 0);
+    else DC_FRONT_D(0, 0);
+#else
+    if (dd) return hipErrorInvalidValue;
+    if (stm0) DC_FRONT(1, 0, false);
+    else DC_FRONT(0, 0, false);
+#endif
   }
+#undef DC_FRONT_D
 #undef DC_FRONT
+  return hipGetLastError();
+}
+
+hipError_t launch_front_fold(hipStream_t st, const FrontDedup& dd, const Board* out, const Range* rng_out,
+                             PerftResult* res) {
+  // (a fixed grid: the record count is on the device; ~200k records at startpos perft(7))
+  hipLaunchKernelGGL(k_front_fold, dim3(256), dim3(256), 0, st, dd, out, rng_out, res);
   return hipGetLastError();
 }
 

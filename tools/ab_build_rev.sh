@@ -21,7 +21,7 @@ make -s libdchess.so
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -I$T/include"
 mkdir -p build/var/$N
 OBJS=""
-for u in dc_perft dc_moves dc_hash dc_txsig dc_api; do
+for u in dc_moves dc_perft dc_hash dc_txsig dc_movegen dc_api; do  # (the Makefile's SRCS)
   if [[ " ${SRCS:-dc_perft} " == *" $u "* ]]; then
     /opt/rocm/bin/hipcc $HIPFLAGS $F -c $T/distributed-chess_amd/csrc/$u.hip -o build/var/$N/$u.o
     OBJS="$OBJS build/var/$N/$u.o"
