@@ -15,7 +15,7 @@ DC_BBPROF_DEFINE(moves)  // measurement builds only (tools/bbprof.py)
 namespace dc {
 
 // ------------------------------------------------------------- validation
-// done != nullptr (a one-block launch whose I/O is pinned host memory, dc_api
+// done != nullptr (a one-block launch whose I/O is pinned host memory, dc_ctx.h
 // HostIo): once the block's results are stored, thread 0 publishes seq to the
 // host flag with a system-scope release, so the caller can spin on the flag
 // instead of synchronising the stream (the live n = 1 consensus call).
@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(256) void k_gen_games_fide(u64 seed, u64 first_game
 // ------------------------------------------------------------- launchers
 
 // ------------------------------------------------------- the live validator
-// One wave resident on one CU, launched on its own stream (dc_api.hip): polls
+// One wave resident on one CU, launched on its own stream (dc_api_validate.hip): polls
 // the request words of a pinned coherent LiveBox (dc_kernels.h) with
 // system-scope loads, validates (and applies) up to 64 moves, one per lane,
 // with the same per-move code as k_validate_ref / k_apply_ref (FIDE:

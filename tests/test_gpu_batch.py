@@ -1,6 +1,6 @@
 """GPU tests of the batch perft (dc_perft_batch / dc_perft_batch_repeat_device):
 several root positions with the same side to move counted as one tree, their
-root moves sharing the divide tags (dc_api.hip; k_expand_top stages up to
+root moves sharing the divide tags (dc_api_perft.hip; k_expand_top stages up to
 DC_PERFT_BATCH_MAX roots).  Pinned by the published FIDE suite tables
 (tests/golden/oracle_golden.json) and, per root move, by the single-position
 perft of the same build and by fastcpu."""

@@ -143,7 +143,7 @@ def test_live_waves_do_not_block_buffer_growth():
     wave's too.  With a 20 s lease on this context and on a second
     one, a perft that grows this context's buffers, a perft on the other
     context, and a context destroyed beside them all finish far inside the
-    lease (every resident wave is stopped first, dc_api.hip LiveHold); the
+    lease (every resident wave is stopped first, dc_api_validate.hip LiveHold); the
     live calls stay right afterwards."""
     import json
     import os
@@ -220,7 +220,7 @@ def test_live_timeout_path_then_fresh_verdicts():
 def test_live_calls_beside_device_work_on_another_thread():
     """a LiveHold on one thread (buffer growth, perft) and live
     calls on another context in a second thread.  live_call decides under
-    g_live_mu whether a hold is active (dc_api.hip), so no wave is started
+    g_live_mu whether a hold is active (dc_api_validate.hip), so no wave is started
     after a hold has stopped them: every step of the working thread finishes
     far inside the 20 s lease, and every live verdict stays exact."""
     import json

@@ -2,8 +2,9 @@
 # A/B baseline from a git revision: dc_perft.hip (and the headers it
 # includes) as of REV (WT: the working tree), linked with the working tree's
 # other objects (measurement only; tools/ab_perft_time.py times the libraries).
-#   [SRCS="dc_perft dc_api"] [PATCH="cmd"] tools/ab_build_rev.sh NAME REV ["FLAGS"]
-# (SRCS: the sources taken from REV, default dc_perft)
+#   [SRCS="dc_perft dc_api_perft"] [PATCH="cmd"] tools/ab_build_rev.sh NAME REV ["FLAGS"]
+# (SRCS: the sources taken from REV, default dc_perft; a host unit dc_api_*
+# only from a REV that has the split host units)
 # -> distributed-chess_amd/build/var/NAME/libdchess.so
 set -e
 N=$1; REV=$2; F=${3:-}
@@ -21,7 +22,8 @@ make -s libdchess.so
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -I$T/include"
 mkdir -p build/var/$N
 OBJS=""
-for u in dc_moves dc_perft dc_hash dc_txsig dc_movegen dc_api; do  # (the Makefile's SRCS)
+for u in dc_moves dc_perft dc_hash dc_txsig dc_movegen dc_api dc_api_validate dc_api_legal dc_api_replay \
+         dc_api_txsig dc_api_perft dc_api_multi; do  # (the Makefile's SRCS)
   if [[ " ${SRCS:-dc_perft} " == *" $u "* ]]; then
     /opt/rocm/bin/hipcc $HIPFLAGS $F -c $T/distributed-chess_amd/csrc/$u.hip -o build/var/$N/$u.o
     OBJS="$OBJS build/var/$N/$u.o"
