@@ -2,6 +2,14 @@
 #include "dc_ctx.h"
 #include "dc_txsig_k.h"
 
+int dcapi::ensure_gtab(dc_ctx* c) {
+  if (c->gtab_ready) return DC_SUCCESS;
+  HIP_TRY(c->gtab.ensure(dc::secp::kGTabEntries));
+  HIP_TRY(dc::launch_secp_gtab(c->stream, c->gtab.p));
+  c->gtab_ready = true;
+  return DC_SUCCESS;
+}
+
 extern "C" {
 
 // ------------------------------------------------ transaction signatures
@@ -16,14 +24,6 @@ const char* dc_sig_verdict_message(uint8_t v) {
     case DC_SIG_WRONG_OWNER: return "invalud turn";    // hotstuff.rs:147 (sic)
   }
   return "unknown verdict";
-}
-
-static int ensure_gtab(dc_ctx* c) {
-  if (c->gtab_ready) return DC_SUCCESS;
-  HIP_TRY(c->gtab.ensure(dc::secp::kGTabEntries));
-  HIP_TRY(dc::launch_secp_gtab(c->stream, c->gtab.p));
-  c->gtab_ready = true;
-  return DC_SUCCESS;
 }
 
 int dc_verify_tx_batch_device(dc_ctx* c, const char* d_strings, const uint32_t* d_str_off, const uint32_t* d_actions,

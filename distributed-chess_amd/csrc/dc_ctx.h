@@ -52,7 +52,11 @@ struct LiveHold {  // dc_api_validate.hip
 // takes the context off the list LiveHold walks (dc_api_validate.hip).
 void live_retire(dc_ctx* c);
 
+// Builds the context's secp256k1 G table on first use (dc_api_txsig.hip).
+int ensure_gtab(dc_ctx* c);
+
 }  // namespace dcapi
+using dcapi::ensure_gtab;
 using dcapi::g_alloc_epoch;
 using dcapi::LiveHold;
 

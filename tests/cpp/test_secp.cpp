@@ -6,7 +6,12 @@
 // Commands (numbers: 64 hex digits, big-endian; strings: hex of their bytes,
 // "-" for the empty string):
 //   fe_mul A B | fe_sqr A | fe_add A B | fe_sub A B | fe_inv A | fe_sqrt A
-//   sc_mul A B | sc_inv A | mulg K | mulq K QX QY | hash W B FX FY TX TY
+//   sc_mul A B | sc_add A B | sc_inv A | mulg K | mulq K QX QY | hash W B FX FY TX TY
+//   split K             -> "K1 K2" (mod n), K = K1 + lambda K2
+//   ecmult U1 U2 QX QY  -> "X Y" of U1 G + U2 Q, or "inf"
+//   verify Z R S QX QY  -> 1 / 0 (ecdsa_verify)
+//   gtab K              -> "X Y" of G-table entry K (decimal)
+//   (the commands of csrc/dc_test_secp.hip's device probe, tests/test_secp_device.py)
 //   tx W B FX FY TX TY SIG PK TURN
 //   timed R   then tx lines, then "end": the G table is built first, then the
 //             parsed transactions are checked R times under a steady_clock;
@@ -139,10 +144,11 @@ int main() {
       u32 t[8];
       rd(t, a);
       sc_canon(x, t);
-      if (op == "sc_mul") {
+      if (op == "sc_mul" || op == "sc_add") {
         rd(t, b);
         sc_canon(y, t);
-        sc_mul(r, x, y);
+        if (op == "sc_mul") sc_mul(r, x, y);
+        else sc_add(r, x, y);
       } else {
         sc_inv(r, x);
       }
@@ -171,6 +177,54 @@ int main() {
         Ge a;
         gej_to_ge(a, r);
         std::cout << wr(a.x.v) << " " << wr(a.y.v) << "\n";
+      }
+    } else if (op == "split") {
+      std::string k;
+      in >> k;
+      Sc s, k1, k2;
+      u32 t[8];
+      rd(t, k);
+      sc_canon(s, t);
+      sc_split_lambda(k1, k2, s);
+      std::cout << wr(k1.v) << " " << wr(k2.v) << "\n";
+    } else if (op == "ecmult" || op == "verify") {
+      std::string h[5];
+      const int nh = op == "ecmult" ? 4 : 5;
+      for (int i = 0; i < nh; ++i) in >> h[i];
+      Sc sc[3];
+      u32 t[8];
+      for (int i = 0; i < nh - 2; ++i) {
+        rd(t, h[i]);
+        sc_canon(sc[i], t);
+      }
+      Ge q;
+      rd(t, h[nh - 2]);
+      fe_canon(q.x, t);
+      rd(t, h[nh - 1]);
+      fe_canon(q.y, t);
+      if (!ge_on_curve(q)) {
+        std::cout << "offcurve\n";
+      } else if (op == "verify") {
+        std::cout << (ecdsa_verify(sc[1], sc[2], sc[0], q, gtab().data()) ? 1 : 0) << "\n";
+      } else {
+        Gej r;
+        ecmult(r, q, sc[1], sc[0], gtab().data());
+        if (r.inf) {
+          std::cout << "inf\n";
+        } else {
+          Ge a;
+          gej_to_ge(a, r);
+          std::cout << wr(a.x.v) << " " << wr(a.y.v) << "\n";
+        }
+      }
+    } else if (op == "gtab") {
+      int k = -1;
+      in >> k;
+      if (k < 0 || k >= kGTabEntries) {
+        std::cout << "?\n";
+      } else {
+        const Ge& g = gtab()[k];
+        std::cout << wr(g.x.v) << " " << wr(g.y.v) << "\n";
       }
     } else if (op == "hash" || op == "tx") {
       std::string w, b, sig, pk;

@@ -22,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(REPO, "oracle"))
 import txsig as T  # noqa: E402
+import secp_model as M  # noqa: E402
 
 BIN = os.path.join(REPO, "distributed-chess_amd", "build", "test_secp")
 
@@ -113,12 +114,11 @@ def test_glv_constants():
     g2 = (2 ** 384 * -b1 + T.N // 2) // T.N
     assert g1 == 0x3086D221A7D46BCDE86C90E49284EB153DAA8A1471E8CA7FE893209A45DBB031
     assert g2 == 0xE4437ED6010E88286F547FA90ABFE4C4221208AC9DF506C61571B4AE8AC47F71
+    # the split itself is restated once, in secp_model.split, from these constants
+    assert (M.LAMBDA, M.BETA, M.A1, M.B1, M.A2, M.B2, M.G1, M.G2) == (LAMBDA, BETA, a1, b1, a2, b2, g1, g2)
     rng = random.Random(9)
     for k in [0, 1, T.N - 1, LAMBDA, T.N // 2] + [rng.randrange(T.N) for _ in range(2000)]:
-        c1 = (k * g1 + 2 ** 383) >> 384
-        c2 = (k * g2 + 2 ** 383) >> 384
-        r2 = (c1 * -b1 + c2 * -b2) % T.N
-        r1 = (k - r2 * LAMBDA) % T.N
+        r1, r2 = M.split(k)
         assert (r1 + LAMBDA * r2) % T.N == k
         for r in (r1, r2):
             assert min(r, T.N - r) < 2 ** 128
@@ -265,3 +265,119 @@ def test_gpu_verify_tx_fixture(engine):
     txs = _fixture()
     got = engine.verify_txs(*pack_txs(txs))
     assert got.tolist() == [t["verdict"] for t in txs]
+
+
+# ------------------------------------------- crafted signatures (txsig_edge.json)
+EDGE_CLASSES = ("sweep", "sweep_twin", "sparse_u1", "u2_fixed", "u2_split", "xr_ge_n", "xr_ge_n_twin", "r_boundary",
+                "r_inf", "arm_double", "arm_inf")
+
+
+def _edge():
+    import json
+    return json.load(open(os.path.join(HERE, "golden", "txsig_edge.json")))["txs"]
+
+
+def _tx_line(t):
+    return (f"tx {_s(t['white'])} {_s(t['black'])} {' '.join(map(str, t['action']))} "
+            f"{_s(t['sig'])} {_s(t['pk'])} {t['turn']}")
+
+
+def test_edge_fixture_coverage():
+    """What tests/golden/make_txsig_edge.py claims, re-derived from the stored
+    u1 / u2 alone: every G-table entry, the GLV sign pairs, every Booth digit,
+    the top window, and the classes with their verdicts."""
+    txs = _edge()
+    path = os.path.join(HERE, "golden", "txsig_edge.json")
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "golden", "txsig_batch.json"))
+    by = {c: [t for t in txs if t["class"] == c] for c in EDGE_CLASSES}
+    assert sum(map(len, by.values())) == len(txs) and all(by.values())
+    assert all(t["turn"] == -1 for t in txs)
+    want = {"sweep": 0, "sweep_twin": 5, "sparse_u1": 0, "u2_fixed": 0, "u2_split": 0, "xr_ge_n": 0, "xr_ge_n_twin": 5,
+            "r_boundary": 5, "r_inf": 5, "arm_double": 5, "arm_inf": 5}
+    assert all(t["verdict"] == want[t["class"]] for t in txs)
+    # table sweep: all 8160 (row, byte != 0) pairs, from the valid sweep vectors alone
+    seen = set()
+    for t in by["sweep"]:
+        seen |= M.u1_rows(int(t["u1"], 16))
+    assert seen == {(i, j) for i in range(32) for j in range(1, 256)}
+    assert len(by["sweep"]) == 256 and len(by["sweep_twin"]) == 32
+    assert any(int(t["u1"], 16) >> 248 == 0xFF for t in by["sweep"])
+    # sparse u1
+    assert {int(t["u1"], 16) for t in by["sparse_u1"]} == {1 << (8 * k) for k in range(32)} | {T.N - 1}
+    # u2 shapes
+    assert [int(t["u2"], 16) for t in by["u2_fixed"]] == M.u2_fixed()
+    shapes = [M.split_shape(int(t["u2"], 16)) for t in by["u2_split"]]
+    assert {(a[0], b[0]) for a, b in shapes} == {(x, y) for x in (False, True) for y in (False, True)}
+    for h in (0, 1):
+        assert {d for sh in shapes for d in sh[h][1]} == set(range(-4, 5))
+        assert any(sh[h][1][M.Q_WINDOWS - 1] for sh in shapes)
+    # x(R) >= n: small r, and the twins differ in s only
+    assert len(by["xr_ge_n"]) >= 3 and all(int(t["sig"][:64], 16) < 64 for t in by["xr_ge_n"])
+    assert {int(t["sig"][:64], 16) for t in by["r_boundary"]} == {T.P - T.N, T.P - T.N - 1}
+    # R at infinity: the three key encodings, and one u1 with its top rows empty
+    assert {len(t["pk"]) for t in by["r_inf"]} == {66, 130} and {t["pk"][:2] for t in by["r_inf"]} & {"06", "07"}
+    assert any(int(t["u1"], 16) >> 192 == 0 for t in by["r_inf"])
+    # the arms: Q = G with u2 = 1 and the low byte of u1 = 1
+    for t in by["arm_double"]:
+        assert t["pk"] == T.pubkey_hex(1) and int(t["u2"], 16) == 1 and int(t["u1"], 16) & 255 == 1
+    assert len(by["arm_inf"]) >= 3
+
+
+def _edge_sample():
+    """At least one vector of every class, about 40 in all."""
+    txs = _edge()
+    first = {}
+    for i, t in enumerate(txs):
+        first.setdefault(t["class"], i)
+    idx = sorted(set(first.values()) | set(range(3, len(txs), max(1, len(txs) // 29))))
+    assert len(idx) <= 42
+    return [txs[i] for i in idx]
+
+
+def test_edge_fixture_matches_oracle():
+    sample = _edge_sample()
+    assert {t["class"] for t in sample} == set(EDGE_CLASSES)
+    for t in sample:
+        assert expected(dict(t, action=tuple(t["action"]))) == t["verdict"], t["class"]
+        z = int.from_bytes(T.message_hash(t["white"], t["black"], tuple(t["action"])), "big") % T.N
+        r, s = int(t["sig"][:64], 16), int(t["sig"][64:], 16)
+        si = pow(s, T.N - 2, T.N)
+        assert (z * si % T.N, r * si % T.N) == (int(t["u1"], 16), int(t["u2"], 16))
+
+
+def test_host_edge_fixture(secp_bin):
+    bad = [(i, t["class"]) for i, t in enumerate(_edge()) if int(secp_bin(_tx_line(t))) != t["verdict"]]
+    assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_gpu_verify_tx_edge_fixture(engine):
+    txs = _edge()
+    got = engine.verify_txs(*pack_txs(txs)).tolist()
+    bad = [(i, t["class"], g) for i, (t, g) in enumerate(zip(txs, got)) if g != t["verdict"]]
+    assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_gpu_verify_tx_edge_fixture_device_permuted(engine):
+    """The same vectors through dc_verify_tx_batch_device, shuffled so that the
+    classes (and their divergent arms) share waves."""
+    txs = _edge()
+    random.Random(77).shuffle(txs)
+    blob, off, acts, turns = pack_txs(txs)
+    n = len(txs)
+    bufs = []
+    try:
+        for arr in (np.frombuffer(blob, np.uint8), off, acts, turns):
+            b = engine.alloc(max(arr.nbytes, 1))
+            bufs.append(b)
+            b.upload(arr)
+        d_v = engine.alloc(n)
+        bufs.append(d_v)
+        engine.verify_txs_device(*bufs[:4], n, d_v)
+        got = d_v.download(np.uint8, n).tolist()
+    finally:
+        for b in bufs:
+            b.free()
+    bad = [(t["class"], t["u1"], g) for t, g in zip(txs, got) if g != t["verdict"]]
+    assert not bad, bad
