@@ -1,5 +1,6 @@
 // dc_api_perft.hip -- the perft driver: dc_perft, dc_perft_shard,
-// dc_perft_batch and the *_repeat_device forms, with their captured graphs.
+// dc_perft_batch and the *_repeat_device forms, with their captured graphs;
+// dc_perft_stats and dc_perft_stats_shard (the plain enqueue path only).
 #include <cstring>
 
 #include "dc_ctx.h"
@@ -704,9 +705,201 @@ int perft_impl(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uin
   return DC_SUCCESS;
 }
 
+// ========================================================= perft statistics
+// dc_perft_stats: the frontier at ply depth - 1 is built as boards, meta and
+// tags by the legacy level chain alone (k_expand_top, then k_level_count,
+// k_chunk_scan and k_level_write per level, the shard cut at split_depth
+// included; no k_front, no move-word level, no k_count3c), and k_leaf_stats
+// classifies every move of every frontier node into the counter block
+// c->pstats.  Speculative capacities and the exact mode are perft_enqueue's.
+constexpr size_t kStatsWords = 256 * (size_t)dc::kPsCount;
+
+int stats_enqueue(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
+                  uint32_t n_shards, bool exact) {
+  const bool fide = rules == DC_RULES_FIDE;
+  const bool sharded = n_shards > 1;
+  const u32 F = depth - 1;              // the frontier's ply; 0: the root itself (depth 1)
+  const u32 Fb = std::max<u32>(F, 1);   // the deepest ply built (ply 1 gives the root moves)
+  const u32 S = shard_level(split_depth, Fb);
+  u32 T = exact ? 1 : std::min<u32>(Fb, 3);
+  if (fide && !exact && T == Fb && Fb == 3) T = 2;  // as perft_shape: a FIDE ply 3 is made on every CU
+  if (sharded) T = std::min(T, S);
+  // (the test knob bounds the speculative top ply as it does the levels below)
+  const u64 cap_T = exact ? kTopCap[T] : std::min(kTopCap[T], c->stats_level_cap);
+  int e = perft_ensure_common(c);
+  if (e != DC_SUCCESS) return e;
+  HIP_TRY(c->pstats.ensure(kStatsWords));
+  if (!c->pstats_host) HIP_TRY(c->pstats_host.alloc(hipHostMallocDefault, kStatsWords * sizeof(u64)));
+  HIP_TRY(c->top_nodes.ensure(kTopCap[1] + kTopCap[2]));
+  HIP_TRY(c->top_tags.ensure(kTopCap[1] + kTopCap[2]));
+  if (fide) HIP_TRY(c->top_meta.ensure(kTopCap[1] + kTopCap[2]));
+  e = ensure_level(c, 0, cap_T, fide);
+  if (e != DC_SUCCESS) return e;
+  dc::TopScratch ts;
+  for (int k = 0; k < 2; ++k) {
+    const u64 off = k ? kTopCap[1] : 0;
+    ts.nodes[k] = c->top_nodes.p + off;
+    ts.tags[k] = c->top_tags.p + off;
+    ts.meta[k] = fide ? c->top_meta.p + off : nullptr;
+    ts.cap[k] = kTopCap[k + 1];
+  }
+  // (the meta goes up under REF too: the device root then always equals the
+  // staged one, which is what root_staged lets a later captured run assume)
+  e = write_root_host(c, pos, 1);
+  if (e == DC_SUCCESS) e = upload_roots(c, 1, true);
+  if (e != DC_SUCCESS) return e;
+  HIP_TRY(hipMemsetAsync(c->pstats.p, 0, kStatsWords * sizeof(u64), c->stream));
+  HIP_TRY(c->timed("expand_top", 0, [&] {
+    return dc::launch_expand_top(c->stream, rules, c->root.p, c->root_meta.p, pos->stm, T, ts, c->nodes[0].p,
+                                 fide ? c->meta[0].p : nullptr, c->tags[0].p, cap_T, c->res.p, c->rng.p + T, nullptr,
+                                 1);
+  }));
+  if (F == 0) {
+    // depth 1: the root's own moves (shard 0 holds them all, as dc_perft_shard's depth 1)
+    if (shard != 0) return DC_SUCCESS;
+    HIP_TRY(c->timed("leaf_stats", 0, [&] {
+      return dc::launch_leaf_stats(c->stream, rules, pos->stm, c->root.p, fide ? c->root_meta.p : nullptr, nullptr,
+                                   nullptr, 1, c->res.p, 1, c->pstats.p);
+    }));
+    return DC_SUCCESS;
+  }
+  u32 L = T;
+  u64 nb = cap_T;
+  int buf = 0;
+  auto take_shard = [&]() -> int {  // this rank's strided shard of level S
+    int e2 = ensure_level(c, buf ^ 1, nb, fide);
+    if (e2 != DC_SUCCESS) return e2;
+    HIP_TRY(dc::launch_gather_shard(c->stream, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr, c->tags[buf].p,
+                                    c->rng.p + L, shard, n_shards, c->nodes[buf ^ 1].p,
+                                    fide ? c->meta[buf ^ 1].p : nullptr, c->tags[buf ^ 1].p));
+    buf ^= 1;
+    return DC_SUCCESS;
+  };
+  if (sharded && L == S) {
+    e = take_shard();
+    if (e != DC_SUCCESS) return e;
+  }
+  while (L < F) {
+    const int stm = pos->stm ^ (L & 1);
+    if (exact) {
+      e = read_range(c, L, &nb);
+      if (e != DC_SUCCESS) return e;
+    }
+    u64 cap_next = std::min(std::min(nb * kBranchBound, kSpecBudget / kNodeBytes), c->stats_level_cap);
+    const u64 nch = std::max<u64>(dc::chunks_for(nb), 1);
+    HIP_TRY(c->counts.ensure(std::max<u64>(nb, 1)));
+    HIP_TRY(c->chunk_sum.ensure(nch));
+    HIP_TRY(c->chunk_base.ensure(nch));
+    HIP_TRY(c->timed("expand_count", 0, [&] {
+      return dc::launch_level_count(c->stream, rules, stm, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
+                                    c->rng.p + L, nb, c->counts.p, c->chunk_sum.p);
+    }));
+    HIP_TRY(c->timed("scan", 0, [&] {
+      return dc::launch_chunk_scan(c->stream, c->chunk_sum.p, c->rng.p + L, c->chunk_base.p, c->rng.p + L + 1,
+                                   exact ? ~0ull : cap_next, c->res.p, 0);
+    }));
+    if (exact) {
+      e = read_range(c, L + 1, &cap_next);
+      if (e != DC_SUCCESS) return e;
+      if (cap_next > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+    }
+    e = ensure_level(c, buf ^ 1, cap_next, fide);
+    if (e != DC_SUCCESS) return e;
+    HIP_TRY(c->timed("expand_write", 0, [&] {
+      return dc::launch_level_write(c->stream, rules, stm, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
+                                    c->tags[buf].p, c->rng.p + L, nb, c->counts.p, c->chunk_base.p,
+                                    c->nodes[buf ^ 1].p, fide ? c->meta[buf ^ 1].p : nullptr, c->tags[buf ^ 1].p,
+                                    cap_next);
+    }));
+    buf ^= 1;
+    ++L;
+    nb = cap_next;
+    if (sharded && L == S) {
+      e = take_shard();
+      if (e != DC_SUCCESS) return e;
+    }
+  }
+  HIP_TRY(c->timed("leaf_stats", 0, [&] {
+    return dc::launch_leaf_stats(c->stream, rules, pos->stm ^ (int)(F & 1), c->nodes[buf].p,
+                                 fide ? c->meta[buf].p : nullptr, c->tags[buf].p, c->rng.p + F, nb, c->res.p, 0,
+                                 c->pstats.p);
+  }));
+  return DC_SUCCESS;
+}
+
+int stats_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
+              uint32_t n_shards, bool exact, dc::PerftResult* out) {
+  int e = stats_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, exact);
+  if (e != DC_SUCCESS) return e;
+  HIP_TRY(hipMemcpyAsync(c->res_host, c->res.p, sizeof(dc::PerftResult), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->pstats_host, c->pstats.p, kStatsWords * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  e = sync_ctx(c);
+  if (e != DC_SUCCESS) return e;
+  *out = *c->res_host;
+  return DC_SUCCESS;
+}
+
+int stats_impl(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
+               uint32_t n_shards, uint64_t* totals, uint64_t* rows, uint16_t* root_moves, uint32_t* n_root) {
+  if (!pos || !totals || rules > DC_RULES_FIDE || n_shards == 0 || shard >= n_shards || pos->stm > 1) return DC_EINVAL;
+  if (depth > 12) return DC_EUNSUPPORTED;
+  std::fill(totals, totals + DC_PS_COUNT, 0);
+  if (n_root) *n_root = 0;
+  if (depth == 0) {
+    totals[DC_PS_NODES] = (shard == 0) ? 1 : 0;
+    return DC_SUCCESS;
+  }
+  dc::PerftResult r;
+  int e = stats_run(c, rules, pos, depth, split_depth, shard, n_shards, false, &r);
+  c->last_stats_exact = e == DC_SUCCESS && r.overflow;
+  if (c->last_stats_exact) e = stats_run(c, rules, pos, depth, split_depth, shard, n_shards, true, &r);
+  if (e != DC_SUCCESS) return e;
+  if (r.overflow) return DC_EUNSUPPORTED;  // more than 256 root moves, or a level beyond 2^32 nodes
+  const u32 nr = r.n_root;
+  if (n_root) *n_root = nr;
+  if (root_moves) std::copy(r.root_moves, r.root_moves + nr, root_moves);
+  const u64* st = c->pstats_host;
+  for (u32 i = 0; i < nr; ++i)
+    for (u32 k = 0; k < DC_PS_COUNT; ++k) totals[k] += st[(size_t)DC_PS_COUNT * i + k];
+  if (rows) std::copy(st, st + (size_t)DC_PS_COUNT * nr, rows);
+  if (c->profiling) {
+    auto it = c->stats.find("leaf_stats");
+    if (it != c->stats.end()) it->second.units += totals[DC_PS_NODES];
+  }
+  return DC_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+// Test hook (not in the header): the most nodes a speculative level of
+// dc_perft_stats may hold (0: unlimited again), so a test can send a small
+// tree through the exact rerun.
+extern "C" __attribute__((visibility("default"))) int dc_test_perft_stats_level_cap(dc_ctx* c, uint64_t cap) {
+  if (!c) return DC_EINVAL;
+  c->stats_level_cap = cap ? cap : ~0ull;
+  return DC_SUCCESS;
+}
+
+// Test hook (not in the header): 1 when the context's last dc_perft_stats took
+// the exact rerun, 0 when its speculative capacities held.
+extern "C" __attribute__((visibility("default"))) int dc_test_perft_stats_last_exact(const dc_ctx* c) {
+  return c ? (int)c->last_stats_exact : -1;
+}
+
+int dc_perft_stats(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint64_t* totals, uint64_t* rows,
+                   uint16_t* root_moves, uint32_t* n_root) {
+  ENTER_WORK(c);
+  return stats_impl(c, rules, pos, depth, 1, 0, 1, totals, rows, root_moves, n_root);
+}
+
+int dc_perft_stats_shard(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,
+                         uint32_t shard, uint32_t n_shards, uint64_t* totals, uint64_t* rows, uint16_t* root_moves,
+                         uint32_t* n_root) {
+  ENTER_WORK(c);
+  return stats_impl(c, rules, pos, depth, split_depth, shard, n_shards, totals, rows, root_moves, n_root);
+}
 
 // Test hook (not in the header): 1 when the context's last perft ran the
 // one-launch front end (k_front), 0 when it took the legacy chain.

@@ -217,6 +217,14 @@ struct dc_ctx {
     u32 n;
   };
   Pinned<RootStage> root_host;
+  // dc_perft_stats: the counters per root move (256 x DC_PS_COUNT u64, kept out
+  // of PerftResult) and their pinned readback block
+  DBuf<u64> pstats;
+  Pinned<u64> pstats_host;
+  // nodes a speculative level of dc_perft_stats may hold (unlimited;
+  // dc_test_perft_stats_level_cap lowers it to test the exact rerun)
+  u64 stats_level_cap = ~0ull;
+  bool last_stats_exact = false;  // the last dc_perft_stats took the exact rerun
   // batch / replay scratch
   DBuf<DevPos> pos;
   DBuf<uint16_t> moves;

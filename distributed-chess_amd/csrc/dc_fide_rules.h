@@ -257,12 +257,14 @@ __device__ __forceinline__ u64 castle_targets(const FPos<STM>& f, const Analysis
   return t;
 }
 
-// Number of legal moves (promotions count 4).
+// Number of legal moves (promotions count 4); `checkers` receives the pieces
+// that give check to the side to move (the analysis' set: perft statistics).
 template <int STM>
-__device__ __forceinline__ u32 fide_count(const Board& b, u32 meta) {
+__device__ __forceinline__ u32 fide_count_checkers(const Board& b, u32 meta, u64& checkers) {
   typedef FDir<STM> FD;
   const FPos<STM> f = fpos<STM>(b);
   const Analysis a = analyse<STM>(f);
+  checkers = a.checkers;
   const u64 notus = ~f.us;
   u32 c = pc(king_attacks(f.K) & notus & ~a.danger);
   if (a.checkers & (a.checkers - 1)) return c;  // double check: king moves only
@@ -316,6 +318,12 @@ __device__ __forceinline__ u32 fide_count(const Board& b, u32 meta) {
   }
   c += pc(castle_targets<STM>(f, a, meta, b));
   return c;
+}
+
+template <int STM>
+__device__ __forceinline__ u32 fide_count(const Board& b, u32 meta) {
+  u64 checkers;
+  return fide_count_checkers<STM>(b, meta, checkers);
 }
 
 // Enumerates legal moves: visit(from, to, promo).  Deterministic order.

@@ -93,6 +93,17 @@ hipError_t launch_gather_shard(hipStream_t st, const Board* in, const uint16_t* 
 hipError_t launch_final(hipStream_t st, u32 rules, int stm, int plies, const Board* nodes, const uint16_t* meta,
                         const uint16_t* tags, const Range* rng, u64 n_bound, u64* divide, const PerftResult* res);
 
+// Perft statistics (dc_perft_stats, dc_perft_stats.hip): every move of every
+// node of the frontier `rng` (ply depth - 1; stm = its side to move) is
+// classified and counted into stats[kPsCount * root tag + counter] (the
+// DC_PS_* counters of include/dchess.h; 256 x kPsCount u64, zeroed by the
+// caller).  root != 0: the frontier is the root position itself (depth 1) and
+// a move's tag is its index in res->root_moves.
+constexpr u32 kPsCount = 11;
+hipError_t launch_leaf_stats(hipStream_t st, u32 rules, int stm, const Board* nodes, const uint16_t* meta,
+                             const uint16_t* tags, const Range* rng, u64 n_bound, const PerftResult* res, u32 root,
+                             u64* stats);
+
 // REF, the last three plies without materialising the final stage's parents:
 // after launch_level_count + launch_chunk_scan on the grandparent level `rng`
 // (next Range = rng_ch = [0, children)), k_level_moves writes every child as a

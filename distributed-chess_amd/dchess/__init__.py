@@ -23,6 +23,12 @@ V_OK, V_NO_PIECE, V_WRONG_TURN, V_ILLEGAL, V_OOR = 0, 1, 2, 3, 4
 RULES_REF, RULES_FIDE = 0, 1
 MOVE_OOR, MOVE_NONE = 0x8000, 0xFFFF
 ST_CHECK, ST_NO_MOVES, ST_DEAD = 1, 2, 4  # dc_legal_moves_batch status bits
+# dc_perft_stats counters (DC_PS_*), and their names in the published tables' column order
+(PS_NODES, PS_CAPTURES, PS_EP, PS_CASTLES, PS_PROMOTIONS, PS_CHECKS, PS_DISCOVERED, PS_DOUBLE, PS_CHECKMATES,
+ PS_STALEMATES, PS_KING_CAPTURES) = range(11)
+PS_COUNT = 11
+PS_NAMES = ("nodes", "captures", "ep", "castles", "promotions", "checks", "discovered", "double", "checkmates",
+            "stalemates", "king_captures")
 CELL_EMPTY = -1
 KINDS = "PNBRQKX"  # cell kind order of the ABI (X = unknown kind string)
 
@@ -103,6 +109,9 @@ def lib():
                                C.POINTER(C.c_uint64)]),
         "dc_perft_shard": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
                                      _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+        "dc_perft_stats": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, C.POINTER(C.c_uint32)]),
+        "dc_perft_stats_shard": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                           _vp, _vp, C.POINTER(C.c_uint32)]),
         "dc_perft_repeat_device": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                              C.c_uint32, _vp]),
         "dc_perft_batch": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
@@ -530,6 +539,19 @@ class Engine:
         _check(lib().dc_perft_shard(self.ctx, rules, _ptr(p), depth, split_depth, shard, n_shards, _ptr(div),
                                     _ptr(rm), C.byref(nr), C.byref(tot)), "dc_perft_shard")
         return int(tot.value), div[:nr.value].copy(), rm[:nr.value].copy()
+
+    def perft_stats(self, pos, depth, rules=RULES_FIDE, split_depth=1, shard=0, n_shards=1):
+        """dc_perft_stats_shard: the published perft tables' columns, each
+        classifying the move that reaches a leaf.  Returns (totals u64[PS_COUNT],
+        rows u64[n_root, PS_COUNT], root_moves u16[n_root])."""
+        p = np.array([pos], POS_DTYPE)
+        tot = np.zeros(PS_COUNT, np.uint64)
+        rows = np.zeros((256, PS_COUNT), np.uint64)
+        rm = np.zeros(256, np.uint16)
+        nr = C.c_uint32()
+        _check(lib().dc_perft_stats_shard(self.ctx, rules, _ptr(p), depth, split_depth, shard, n_shards, _ptr(tot),
+                                          _ptr(rows), _ptr(rm), C.byref(nr)), "dc_perft_stats_shard")
+        return tot, rows[:nr.value].copy(), rm[:nr.value].copy()
 
     def perft_repeat_device(self, pos, depth, split_depth, shard, n_shards, n_runs, d_out, rules=RULES_REF):
         """dc_perft_repeat_device: n_runs perfts enqueued back to back, run i's

@@ -342,6 +342,42 @@ int dc_perft_shard(dc_ctx* ctx, uint32_t rules, const dc_pos* pos, uint32_t dept
                    uint32_t shard, uint32_t n_shards, uint64_t* divide, uint16_t* root_moves,
                    uint32_t* n_root, uint64_t* total);
 
+/* ------------------------------------------------------- perft statistics
+ * The columns of the published perft tables: every counter classifies the LAST
+ * move of a line, the move that reaches a leaf at ply `depth`.  totals
+ * (required) has room for DC_PS_COUNT entries; rows (NULL to skip) for
+ * 256 * DC_PS_COUNT: rows[DC_PS_COUNT * i + k] is counter k below root move
+ * root_moves[i].  root_moves / n_root are dc_perft's, in its root-move order.
+ * DC_RULES_FIDE: CAPTURES includes en passant; CASTLES = king moves of two
+ * files; CHECKS = the side now to move has its king attacked (discovered and
+ * double checks included); DOUBLE = two or more checkers; DISCOVERED = exactly
+ * one checker that is not the piece that moved (not on the move's `to` square,
+ * where a promoted piece stands; not the castled rook; an en-passant capture
+ * whose check runs through the vacated squares is discovered); CHECKMATES /
+ * STALEMATES = the child has no legal move, with / without check; a side with
+ * no king is never in check.  DC_RULES_REF (no check concept): NODES,
+ * CAPTURES (dc_apply_batch's capture bit) and KING_CAPTURES; the rest are 0.
+ * Depth 0: NODES 1 (shard 0), n_root 0; depth 1 classifies the root's own
+ * moves.  Errors as dc_perft_shard's; totals and rows summed over the shards of
+ * one (split_depth, n_shards) equal the unsharded result exactly. */
+#define DC_PS_NODES         0  /* leaf moves = dc_perft's count */
+#define DC_PS_CAPTURES      1  /* target square held a piece, or en passant */
+#define DC_PS_EP            2
+#define DC_PS_CASTLES       3
+#define DC_PS_PROMOTIONS    4  /* each of the four promotion moves counts once */
+#define DC_PS_CHECKS        5  /* the move leaves the opponent's king attacked */
+#define DC_PS_DISCOVERED    6
+#define DC_PS_DOUBLE        7
+#define DC_PS_CHECKMATES    8
+#define DC_PS_STALEMATES    9
+#define DC_PS_KING_CAPTURES 10 /* REF: the captured piece is a king; FIDE: 0 */
+#define DC_PS_COUNT         11
+int dc_perft_stats(dc_ctx* ctx, uint32_t rules, const dc_pos* pos, uint32_t depth, uint64_t* totals,
+                   uint64_t* rows, uint16_t* root_moves, uint32_t* n_root);
+int dc_perft_stats_shard(dc_ctx* ctx, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,
+                         uint32_t shard, uint32_t n_shards, uint64_t* totals, uint64_t* rows,
+                         uint16_t* root_moves, uint32_t* n_root);
+
 /* n_runs perfts of *pos (depth >= 2; shard as dc_perft_shard) enqueued back to
  * back on the context stream with no host round trip between them.  Run i
  * leaves its result in DEVICE memory d_out[258 i .. 258 i + 258):

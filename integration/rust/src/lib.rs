@@ -66,6 +66,18 @@ pub mod sys {
     pub const DC_ST_CHECK: u8 = 1;
     pub const DC_ST_NO_MOVES: u8 = 2;
     pub const DC_ST_DEAD: u8 = 4;
+    pub const DC_PS_NODES: usize = 0;
+    pub const DC_PS_CAPTURES: usize = 1;
+    pub const DC_PS_EP: usize = 2;
+    pub const DC_PS_CASTLES: usize = 3;
+    pub const DC_PS_PROMOTIONS: usize = 4;
+    pub const DC_PS_CHECKS: usize = 5;
+    pub const DC_PS_DISCOVERED: usize = 6;
+    pub const DC_PS_DOUBLE: usize = 7;
+    pub const DC_PS_CHECKMATES: usize = 8;
+    pub const DC_PS_STALEMATES: usize = 9;
+    pub const DC_PS_KING_CAPTURES: usize = 10;
+    pub const DC_PS_COUNT: usize = 11;
     pub const DC_SIG_OK: u8 = 0;
     pub const DC_SIG_BAD_SIG_HEX: u8 = 1;
     pub const DC_SIG_BAD_SIG: u8 = 2;
@@ -148,6 +160,11 @@ pub mod sys {
         pub fn dc_perft_shard(ctx: *mut dc_ctx, rules: u32, pos: *const dc_pos, depth: u32, split_depth: u32,
                               shard: u32, n_shards: u32, divide: *mut u64, root_moves: *mut u16,
                               n_root: *mut u32, total: *mut u64) -> c_int;
+        pub fn dc_perft_stats(ctx: *mut dc_ctx, rules: u32, pos: *const dc_pos, depth: u32, totals: *mut u64,
+                              rows: *mut u64, root_moves: *mut u16, n_root: *mut u32) -> c_int;
+        pub fn dc_perft_stats_shard(ctx: *mut dc_ctx, rules: u32, pos: *const dc_pos, depth: u32, split_depth: u32,
+                                    shard: u32, n_shards: u32, totals: *mut u64, rows: *mut u64,
+                                    root_moves: *mut u16, n_root: *mut u32) -> c_int;
         pub fn dc_perft_repeat_device(ctx: *mut dc_ctx, rules: u32, pos: *const dc_pos, depth: u32,
                                       split_depth: u32, shard: u32, n_shards: u32, n_runs: u32,
                                       d_out: *mut u64) -> c_int;
@@ -316,6 +333,24 @@ impl Engine {
                                            n_plies, std::ptr::null_mut(), std::ptr::null_mut(),
                                            info.as_mut_ptr(), &mut st) }, "dc_replay_info")?;
         Ok((info, st))
+    }
+
+    /// The published perft tables' columns for one position (dc_perft_stats_shard;
+    /// split_depth 1, shard 0 of 1 is the whole tree).  Returns (totals, one row
+    /// of DC_PS_COUNT counters per root move, the root moves).
+    pub fn perft_stats(&self, rules: u32, pos: &sys::dc_pos, depth: u32, split_depth: u32, shard: u32, n_shards: u32)
+                       -> Result<([u64; sys::DC_PS_COUNT], Vec<[u64; sys::DC_PS_COUNT]>, Vec<u16>), DcError> {
+        let mut totals = [0u64; sys::DC_PS_COUNT];
+        let mut rows = vec![[0u64; sys::DC_PS_COUNT]; 256];
+        let mut root_moves = vec![0u16; 256];
+        let mut n_root = 0u32;
+        check(unsafe { sys::dc_perft_stats_shard(self.0, rules, pos, depth, split_depth, shard, n_shards,
+                                                 totals.as_mut_ptr(), rows.as_mut_ptr() as *mut u64,
+                                                 root_moves.as_mut_ptr(), &mut n_root) }, "dc_perft_stats_shard")?;
+        let n = (n_root as usize).min(256);
+        rows.truncate(n);
+        root_moves.truncate(n);
+        Ok((totals, rows, root_moves))
     }
 }
 
