@@ -245,6 +245,11 @@ struct dc_ctx {
   std::string hist_text;   // the escaped start history (host side of the H2D copy)
   DBuf<uint8_t> hashes;
   DBuf<u64> bitmap, digests, stats5;
+  // dc_replay_outcome*: the position history of one chunk of games ([slot][word][game],
+  // dc_outcome.hip), the block records behind their totals, the host form's outcomes
+  DBuf<u64> outcome_hist, outcome_part, outcomes;
+  // games adjudicated per launch: 1 GiB of history (dc_test_outcome_chunk_games lowers it)
+  u32 outcome_chunk_games = 177664;
   // the state hash's replay pre-pass is skipped past this many bytes of its
   // buffers (unlimited; dc_test_hash_prepass_max lowers it to test the fallback)
   u64 hash_prepass_max = ~0ull;

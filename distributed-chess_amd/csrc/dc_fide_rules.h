@@ -767,6 +767,40 @@ __device__ __forceinline__ u32 fide_count_split(const Board& b, u32 meta, SensAt
   return c;
 }
 
+constexpr u64 kDarkSquares = 0xAA55AA55AA55AA55ull;  // x + y even
+
+// Insufficient material: kings, knights and bishops only, and at most one of
+// the latter two in all, or no knight and every bishop on one square colour.
+__device__ __forceinline__ bool fide_insufficient(const Board& b) {
+  const u64 lo = b.b1, mid = b.b2, hi = b.b3;
+  const u64 occ = lo | mid | hi;
+  const u64 N = mid & ~(lo | hi), K = lo & mid & ~hi, B = hi & lo & ~mid;
+  const u32 heavy = pc(occ & ~(N | K | B));
+  const u32 minors = pc(N | B);
+  const u32 nn = pc(N), bd = pc(B & kDarkSquares), bl = pc(B & ~kDarkSquares);
+  return heavy == 0 && (minors <= 1 || (nn == 0 && (bd == 0 || bl == 0)));
+}
+
+// Is at least one en-passant capture onto meta's target square legal for the
+// side to move?  (fide_make sets the square after every double push; FIDE 9.2.2
+// counts it into a position's identity only when it can be used.)
+template <int STM>
+__device__ __forceinline__ bool fide_ep_capturable(const Board& b, u32 meta) {
+  typedef FDir<STM> FD;
+  const int ep = meta_ep(meta);
+  if (ep < 0) return false;
+  const FPos<STM> f = fpos<STM>(b);
+  const int ksq = f.K ? lsb(f.K) : -1;
+  u64 cand = pawn_attacks<1 - STM>(1ull << ep) & f.P;
+  bool any = false;
+  while (cand) {
+    const int s = lsb(cand);
+    cand &= cand - 1;
+    any |= ep_legal<STM>(f, ksq, s, ep, ep - FD::F);
+  }
+  return any;
+}
+
 // Promotion piece -> kind code (1 N, 2 B, 3 R, 4 Q).
 __device__ __forceinline__ u32 promo_code(int promo) {
   return promo == 1 ? KC_N : promo == 2 ? KC_B : promo == 3 ? KC_R : KC_Q;

@@ -85,8 +85,6 @@ struct RefGen {
   }
 };
 
-constexpr u64 kDarkSquares = 0xAA55AA55AA55AA55ull;  // x + y even
-
 template <int STM>
 __device__ __forceinline__ u32 fide_in_check(const Board& b) {
   const FPos<STM> f = fpos<STM>(b);
@@ -101,18 +99,8 @@ __device__ __forceinline__ u32 fide_in_check(const Board& b) {
   return (k != 0 && att != 0) ? (u32)ST_CHECK : 0u;
 }
 
-// Insufficient material: kings, knights and bishops only, and at most one of
-// the latter two in all, or no knight and every bishop on one square colour.
-__device__ __forceinline__ u32 fide_dead(const Board& b) {
-  const u64 lo = b.b1, mid = b.b2, hi = b.b3;
-  const u64 occ = lo | mid | hi;
-  const u64 N = mid & ~(lo | hi), K = lo & mid & ~hi, B = hi & lo & ~mid;
-  const u32 heavy = pc(occ & ~(N | K | B));
-  const u32 minors = pc(N | B);
-  const u32 nn = pc(N), bd = pc(B & kDarkSquares), bl = pc(B & ~kDarkSquares);
-  const bool dead = heavy == 0 && (minors <= 1 || (nn == 0 && (bd == 0 || bl == 0)));
-  return dead ? (u32)ST_DEAD : 0u;
-}
+// DC_ST_DEAD: insufficient material (dc_fide_rules.h fide_insufficient).
+__device__ __forceinline__ u32 fide_dead(const Board& b) { return fide_insufficient(b) ? (u32)ST_DEAD : 0u; }
 
 template <int STM, class Sink>
 __device__ __forceinline__ void fide_list_stm(const Board& b, u32 meta, Sink&& sink) {

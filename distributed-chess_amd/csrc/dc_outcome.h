@@ -1,0 +1,30 @@
+// dc_outcome.h -- launch wrappers of the game-adjudication kernel (dc_outcome.hip).
+#pragma once
+#include "dc_kernels.h"
+
+namespace dc {
+
+// dc_game_outcome (include/dchess.h) as the kernel stores it: one u64 per game,
+// result | repeats << 8 | halfmove << 16 | end_ply << 32.
+constexpr u32 kOutcomeBlock = 256;   // games per block, one lane each
+constexpr u32 kOutcomeSlots = 151;   // half-move clocks 0..150
+constexpr u32 kOutcomeKeyWords = 5;  // the four bitboards, and stm | castle | usable ep
+constexpr u32 kOutcomeResults = 7;   // DC_GO_COUNT
+// a block's record: validated, accepted, rejected, digest sum, digest xor, then
+// the games per result
+constexpr u32 kOutcomeRecord = 5 + kOutcomeResults;
+
+// u64 words of position history for `games` lanes, laid out [slot][word][game].
+inline size_t outcome_history_words(u32 games) { return (size_t)kOutcomeSlots * kOutcomeKeyWords * games; }
+
+// Adjudicates games [first, first + count) of the batch (first a multiple of
+// kOutcomeBlock): outcomes, digests, the bitmap's word columns and the block
+// records of those games.  history holds outcome_history_words(hist_stride)
+// words, hist_stride >= count.
+hipError_t launch_replay_outcome(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
+                                 u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
+                                 u64* outcomes, u64* bitmap, u64* digests, u64* partial);
+// totals[kOutcomeRecord] = the n_blocks block records combined (xor for the digest xor).
+hipError_t launch_outcome_reduce(hipStream_t st, const u64* partial, u32 n_blocks, u64* totals);
+
+}  // namespace dc

@@ -23,6 +23,10 @@ V_OK, V_NO_PIECE, V_WRONG_TURN, V_ILLEGAL, V_OOR = 0, 1, 2, 3, 4
 RULES_REF, RULES_FIDE = 0, 1
 MOVE_OOR, MOVE_NONE = 0x8000, 0xFFFF
 ST_CHECK, ST_NO_MOVES, ST_DEAD = 1, 2, 4  # dc_legal_moves_batch status bits
+# dc_replay_outcome results (DC_GO_*), and their names
+GO_ONGOING, GO_WHITE_WINS, GO_BLACK_WINS, GO_STALEMATE, GO_DEAD, GO_FIVEFOLD, GO_SEVENTYFIVE = range(7)
+GO_COUNT = 7
+GO_NAMES = ("ongoing", "white_wins", "black_wins", "stalemate", "dead", "fivefold", "seventyfive")
 # dc_perft_stats counters (DC_PS_*), and their names in the published tables' column order
 (PS_NODES, PS_CAPTURES, PS_EP, PS_CASTLES, PS_PROMOTIONS, PS_CHECKS, PS_DISCOVERED, PS_DOUBLE, PS_CHECKMATES,
  PS_STALEMATES, PS_KING_CAPTURES) = range(11)
@@ -35,6 +39,8 @@ KINDS = "PNBRQKX"  # cell kind order of the ABI (X = unknown kind string)
 POS_DTYPE = np.dtype([("bb", "<u8", (4,)), ("stm", "u1"), ("castle", "u1"), ("ep", "i1"), ("r0", "u1"),
                       ("r1", "<u4")])
 assert POS_DTYPE.itemsize == 40
+OUTCOME_DTYPE = np.dtype([("result", "u1"), ("repeats", "u1"), ("halfmove", "<u2"), ("end_ply", "<u4")])
+assert OUTCOME_DTYPE.itemsize == 8
 
 
 class DChessError(RuntimeError):
@@ -99,6 +105,11 @@ def lib():
                                      C.POINTER(_Stats)]),
         "dc_replay_info_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
                                             C.POINTER(_Stats)]),
+        "dc_replay_outcome": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                        C.POINTER(_Stats)]),
+        "dc_replay_outcome_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                               C.POINTER(_Stats)]),
+        "dc_fen_clocks": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "dc_history_append": (C.c_int, [C.c_char_p, _vp, _vp, C.c_uint32, C.c_size_t, _vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
         "dc_gen_games": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -290,6 +301,13 @@ def pos_from_fen(fen):
     return p[0]
 
 
+def fen_clocks(fen):
+    """dc_fen_clocks: (half-move clock, full-move number) of a FEN; (0, 1) where absent."""
+    hm, fm = C.c_uint32(), C.c_uint32()
+    _check(lib().dc_fen_clocks(fen.encode(), C.byref(hm), C.byref(fm)), "dc_fen_clocks")
+    return int(hm.value), int(fm.value)
+
+
 def move_pack(fx, fy, tx, ty):
     return int(lib().dc_move_pack(fx, fy, tx, ty))
 
@@ -460,6 +478,36 @@ class Engine:
         _check(lib().dc_replay_device(self.ctx, rules, None, _dptr(d_moves), n_games, n_plies, _dptr(d_bitmap),
                                       _dptr(d_digests), C.byref(st)), "dc_replay_device")
         return {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def replay_outcome(self, moves, start=None, start_halfmove=0, want_bitmap=True, want_digests=True):
+        """dc_replay_outcome (RULES_FIDE): replay that adjudicates every game.
+        moves: uint16 [n_plies, n_games] ply-major.  Returns (outcomes
+        OUTCOME_DTYPE [n_games], bitmap, digests, counts u64[GO_COUNT], stats dict)."""
+        moves = np.ascontiguousarray(moves, np.uint16)
+        n_plies, n_games = moves.shape
+        words = (n_games + 63) // 64
+        out = np.zeros(n_games, OUTCOME_DTYPE)
+        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
+        dig = np.zeros(n_games, np.uint64) if want_digests else None
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        _check(lib().dc_replay_outcome(self.ctx, _ptr(sp), int(start_halfmove), _ptr(moves), n_games, n_plies,
+                                       _ptr(out), _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st)),
+               "dc_replay_outcome")
+        return out, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def replay_outcome_device(self, d_moves, n_games, n_plies, d_outcomes, d_bitmap=None, d_digests=None,
+                              start=None, start_halfmove=0):
+        """dc_replay_outcome_device on DeviceBuffers or raw device addresses
+        (d_outcomes: 8 bytes a game).  Returns (counts u64[GO_COUNT], stats dict)."""
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        _check(lib().dc_replay_outcome_device(self.ctx, _ptr(sp), int(start_halfmove), _dptr(d_moves), n_games,
+                                              n_plies, _dptr(d_outcomes), _dptr(d_bitmap), _dptr(d_digests),
+                                              _ptr(counts), C.byref(st)), "dc_replay_outcome_device")
+        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
 
     def state_hash(self, moves, names, start=None, history=""):
         """keccak256(serde_json(final GameState)) of every game of a replay batch

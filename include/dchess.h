@@ -130,7 +130,8 @@ int dc_version(void);
 /* Per-kernel HIP-event timing (enable, read, reset).  Kernel names:
  * "validate", "replay", "gen_games", "expand_count", "expand_write", "count1", "count2",
  * "legal_count" (units: positions), "legal_emit" (units: moves); beside them
- * "legal_scan", "legal_fixup" and, for batches of at most 256, "legal_small". */
+ * "legal_scan", "legal_fixup" and, for batches of at most 256, "legal_small";
+ * "replay_outcome" (units: moves consumed). */
 int dc_ctx_set_profiling(dc_ctx* ctx, int enable);
 int dc_ctx_kernel_stats(dc_ctx* ctx, const char* kernel, dc_kernel_stats* out);
 int dc_ctx_reset_stats(dc_ctx* ctx);
@@ -249,6 +250,67 @@ int dc_replay_info_device(dc_ctx* ctx, uint32_t rules, const dc_pos* start, cons
  * DC_EINVAL if out_cap is too small (out_cap = 0 only sizes it). */
 int dc_history_append(const char* history, const uint16_t* moves, const uint8_t* info, uint32_t n_plies,
                       size_t stride, char* out, size_t out_cap, size_t* out_len);
+
+/* ------------------------------------------------------------ game outcome
+ * dc_replay under DC_RULES_FIDE that also adjudicates: for every game, the
+ * ply at which it ended and how.  A replica replaying a move log calls it
+ * before it votes; plies past end_ply belong to no game and are to be rejected.
+ *
+ * Layout as dc_replay: moves ply-major (moves[ply*n_games + g]), start NULL =
+ * startpos, DC_MOVE_NONE skipped.  A rejected move leaves the position, the
+ * clock and the occurrence counts untouched; it counts in stats->validated and
+ * stats->rejected.
+ * Terminal check: on the start position and on the position after every
+ * accepted move, in the priority checkmate > stalemate > dead > fivefold >
+ * seventy-five (checkmate on the move that completes 75 moves wins, FIDE
+ * 9.6.2; the others are all draws, the order only fixes the code).  Once a game
+ * is terminal its remaining moves are neither validated nor applied, their
+ * bitmap bits are 0, they do not count in stats, and the game's digest is the
+ * terminal position's (dc_replay's digest of the game cut at end_ply).
+ * Half-move clock: starts at start_halfmove (<= 150, else DC_EINVAL), returns
+ * to 0 on a pawn move or a capture (en passant included), else goes up by 1.
+ * Position identity (FIDE 9.2.2): same piece placement, side to move and
+ * castling rights; the en-passant square is part of it only where at least one
+ * en-passant capture is legal (a capture by a pinned pawn is not).
+ * Occurrences are counted from start on, start being occurrence 1 (earlier
+ * positions are unknown); only positions since the last clock reset can match.
+ * Positions are compared whole, never by hash.  The claimable draws are left
+ * to the caller: repeats >= 3 (threefold) and halfmove >= 100 (fifty moves) on
+ * the final position do not end a game.
+ * counts (optional, DC_GO_COUNT entries): counts[k] = games with result k,
+ * reduced on the device.  bitmap, digests and stats as dc_replay's (optional);
+ * outcomes is required.  Any n_games dc_replay serves: the games are
+ * adjudicated in chunks, so the history memory stays bounded.
+ * Kernel timing name: "replay_outcome" (units: moves consumed).
+ * The _device form takes d_moves, d_outcomes, d_bitmap and d_digests in device
+ * memory; counts and stats stay host pointers. */
+#define DC_GO_ONGOING      0
+#define DC_GO_WHITE_WINS   1  /* Black is checkmated */
+#define DC_GO_BLACK_WINS   2  /* White is checkmated */
+#define DC_GO_STALEMATE    3
+#define DC_GO_DEAD         4  /* DC_ST_DEAD's definition, unchanged */
+#define DC_GO_FIVEFOLD     5  /* FIDE 9.6.1 */
+#define DC_GO_SEVENTYFIVE  6  /* FIDE 9.6.2: half-move clock reached 150 */
+#define DC_GO_COUNT        7
+typedef struct dc_game_outcome {
+  uint8_t result;    /* DC_GO_* */
+  uint8_t repeats;   /* occurrences of the FINAL position, itself included (>= 1) */
+  uint16_t halfmove; /* half-move clock of the final position */
+  uint32_t end_ply;  /* plies consumed: index + 1 of the move that ended the game,
+                        0 if the start position is already terminal, n_plies if ongoing */
+} dc_game_outcome;   /* 8 bytes */
+/* outcomes / d_outcomes: dc_game_outcome[n_games], declared void* (the Rust
+ * binding's type check, tests/test_abi.py, knows a fixed set of struct names). */
+int dc_replay_outcome(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, const uint16_t* moves,
+                      uint32_t n_games, uint32_t n_plies, void* outcomes, uint64_t* bitmap, uint64_t* digests,
+                      uint64_t* counts, dc_replay_stats* stats);
+int dc_replay_outcome_device(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, const uint16_t* d_moves,
+                             uint32_t n_games, uint32_t n_plies, void* d_outcomes, uint64_t* d_bitmap,
+                             uint64_t* d_digests, uint64_t* counts, dc_replay_stats* stats);
+/* The half-move clock and full-move number of a FEN (its fifth and sixth
+ * fields, which dc_pos_from_fen does not keep), on the host; absent fields
+ * give 0 and 1.  Either output may be NULL. */
+int dc_fen_clocks(const char* fen, uint32_t* halfmove, uint32_t* fullmove);
 
 /* Seeded synthetic games: rng = splitmix64 from seed ^ game_id;
  * per ply one draw r: (r & 0xFF) < noise_per_256 -> move (r>>8)&0xFFF, else the

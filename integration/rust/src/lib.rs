@@ -44,6 +44,16 @@ pub mod sys {
         pub units: u64,
     }
 
+    /// One game's adjudication (dc_replay_outcome), 8 bytes.
+    #[repr(C)]
+    #[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+    pub struct dc_game_outcome {
+        pub result: u8,
+        pub repeats: u8,
+        pub halfmove: u16,
+        pub end_ply: u32,
+    }
+
     pub enum dc_ctx {}
 
     pub const DC_SUCCESS: c_int = 0;
@@ -66,6 +76,14 @@ pub mod sys {
     pub const DC_ST_CHECK: u8 = 1;
     pub const DC_ST_NO_MOVES: u8 = 2;
     pub const DC_ST_DEAD: u8 = 4;
+    pub const DC_GO_ONGOING: u8 = 0;
+    pub const DC_GO_WHITE_WINS: u8 = 1;
+    pub const DC_GO_BLACK_WINS: u8 = 2;
+    pub const DC_GO_STALEMATE: u8 = 3;
+    pub const DC_GO_DEAD: u8 = 4;
+    pub const DC_GO_FIVEFOLD: u8 = 5;
+    pub const DC_GO_SEVENTYFIVE: u8 = 6;
+    pub const DC_GO_COUNT: usize = 7;
     pub const DC_PS_NODES: usize = 0;
     pub const DC_PS_CAPTURES: usize = 1;
     pub const DC_PS_EP: usize = 2;
@@ -127,6 +145,14 @@ pub mod sys {
         pub fn dc_replay_device(ctx: *mut dc_ctx, rules: u32, start: *const dc_pos, d_moves: *const u16,
                                 n_games: u32, n_plies: u32, d_bitmap: *mut u64, d_digests: *mut u64,
                                 stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_replay_outcome(ctx: *mut dc_ctx, start: *const dc_pos, start_halfmove: u32, moves: *const u16,
+                                 n_games: u32, n_plies: u32, outcomes: *mut c_void, bitmap: *mut u64,
+                                 digests: *mut u64, counts: *mut u64, stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_replay_outcome_device(ctx: *mut dc_ctx, start: *const dc_pos, start_halfmove: u32,
+                                        d_moves: *const u16, n_games: u32, n_plies: u32, d_outcomes: *mut c_void,
+                                        d_bitmap: *mut u64, d_digests: *mut u64, counts: *mut u64,
+                                        stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_fen_clocks(fen: *const c_char, halfmove: *mut u32, fullmove: *mut u32) -> c_int;
         pub fn dc_replay_info(ctx: *mut dc_ctx, rules: u32, start: *const dc_pos, moves: *const u16, n_games: u32,
                               n_plies: u32, bitmap: *mut u64, digests: *mut u64, info: *mut u8,
                               stats: *mut dc_replay_stats) -> c_int;
@@ -335,6 +361,24 @@ impl Engine {
         Ok((info, st))
     }
 
+    /// Adjudicates one game's move log under the standard rules before a vote
+    /// (dc_replay_outcome, n_games = 1): where the game ended and how, and the
+    /// counters of the plies up to there.  Plies at or past `end_ply` of a
+    /// finished game belong to no game: the caller rejects them.
+    pub fn replay_outcome(&self, start: Option<&sys::dc_pos>, start_halfmove: u32, moves: &[u16])
+                          -> Result<(sys::dc_game_outcome, sys::dc_replay_stats), DcError> {
+        let n_plies = u32::try_from(moves.len()).map_err(|_| DcError {
+            status: sys::DC_EINVAL, what: "dc_replay_outcome", text: "move log longer than u32::MAX plies".into() })?;
+        let mut out = sys::dc_game_outcome::default();
+        let mut st = sys::dc_replay_stats::default();
+        let sp = start.map_or(std::ptr::null(), |p| p as *const sys::dc_pos);
+        check(unsafe { sys::dc_replay_outcome(self.0, sp, start_halfmove, moves.as_ptr(), 1, n_plies,
+                                              &mut out as *mut sys::dc_game_outcome as *mut c_void,
+                                              std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+                                              &mut st) }, "dc_replay_outcome")?;
+        Ok((out, st))
+    }
+
     /// The published perft tables' columns for one position (dc_perft_stats_shard;
     /// split_depth 1, shard 0 of 1 is the whole tree).  Returns (totals, one row
     /// of DC_PS_COUNT counters per root move, the root moves).
@@ -377,6 +421,15 @@ pub fn history_append(history: &str, moves: &[u16], info: &[u8]) -> Result<Strin
     out.truncate(len);
     String::from_utf8(out)
         .map_err(|_| DcError { status: sys::DC_EINVAL, what: "history_append", text: "not UTF-8".into() })
+}
+
+/// (half-move clock, full-move number) of a FEN (dc_fen_clocks, host only).
+pub fn fen_clocks(fen: &str) -> Result<(u32, u32), DcError> {
+    let f = CString::new(fen)
+        .map_err(|_| DcError { status: sys::DC_EINVAL, what: "fen_clocks", text: "NUL in FEN".into() })?;
+    let (mut hm, mut fm) = (0u32, 0u32);
+    check(unsafe { sys::dc_fen_clocks(f.as_ptr(), &mut hm, &mut fm) }, "dc_fen_clocks")?;
+    Ok((hm, fm))
 }
 
 /// keccak256 (alloy) of one byte string, on the host.
