@@ -1,4 +1,4 @@
-// dc_api_outcome.hip -- game adjudication (dc_replay_outcome*) and the FEN clocks.
+// dc_api_outcome.hip -- game adjudication (dc_replay_outcome*, dc_replay_san*) and the FEN clocks.
 #include <cstring>
 
 #include "dc_ctx.h"
@@ -13,9 +13,11 @@ u32 chunk_games(const dc_ctx* c) {
   return std::max<u32>(k, dc::kOutcomeBlock);
 }
 
+// d_san == nullptr: k_replay_outcome; else k_replay_san, which also fills d_san.
 int outcome_impl(dc_ctx* c, const dc_pos* start, uint32_t start_halfmove, const uint16_t* d_moves, uint32_t n_games,
-                 uint32_t n_plies, u64* d_outcomes, u64* d_bitmap, u64* d_digests, uint64_t* counts,
+                 uint32_t n_plies, u64* d_outcomes, uint8_t* d_san, u64* d_bitmap, u64* d_digests, uint64_t* counts,
                  dc_replay_stats* stats) {
+  const char* name = d_san ? "replay_san" : "replay_outcome";
   dc_pos s;
   if (start) s = *start;
   else dc_startpos(&s);
@@ -31,10 +33,14 @@ int outcome_impl(dc_ctx* c, const dc_pos* start, uint32_t start_halfmove, const 
     // the chunks share the history: they run one after another on the stream
     for (u64 first = 0; first < n_games; first += chunk) {
       const u32 count = (u32)std::min<u64>(chunk, n_games - first);
-      HIP_TRY(c->timed("replay_outcome", 0, [&] {
-        return dc::launch_replay_outcome(c->stream, reinterpret_cast<const DevPos&>(s), start_halfmove, d_moves,
-                                         n_games, n_plies, (u32)first, count, c->outcome_hist.p, chunk, d_outcomes,
-                                         d_bitmap, d_digests, partial);
+      HIP_TRY(c->timed(name, 0, [&] {
+        const DevPos& sp = reinterpret_cast<const DevPos&>(s);
+        return d_san ? dc::launch_replay_san(c->stream, sp, start_halfmove, d_moves, n_games, n_plies, (u32)first,
+                                             count, c->outcome_hist.p, chunk, d_outcomes, d_san, d_bitmap, d_digests,
+                                             partial)
+                     : dc::launch_replay_outcome(c->stream, sp, start_halfmove, d_moves, n_games, n_plies, (u32)first,
+                                                 count, c->outcome_hist.p, chunk, d_outcomes, d_bitmap, d_digests,
+                                                 partial);
       }));
     }
     HIP_TRY(dc::launch_outcome_reduce(c->stream, partial, n_blocks, totals));
@@ -52,7 +58,7 @@ int outcome_impl(dc_ctx* c, const dc_pos* start, uint32_t start_halfmove, const 
   if (counts)
     for (u32 k = 0; k < DC_GO_COUNT; ++k) counts[k] = h[5 + k];
   // the unit count: moves consumed (validated plies)
-  if (c->profiling && n_games) c->stats["replay_outcome"].units += h[0];
+  if (c->profiling && n_games) c->stats[name].units += h[0];
   return DC_SUCCESS;
 }
 
@@ -67,7 +73,7 @@ int dc_replay_outcome_device(dc_ctx* c, const dc_pos* start, uint32_t start_half
                              uint64_t* d_digests, uint64_t* counts, dc_replay_stats* stats) {
   ENTER_WORK(c);
   if ((n_games && n_plies && !d_moves) || (n_games && !d_outcomes)) return DC_EINVAL;
-  return outcome_impl(c, start, start_halfmove, d_moves, n_games, n_plies, static_cast<u64*>(d_outcomes),
+  return outcome_impl(c, start, start_halfmove, d_moves, n_games, n_plies, static_cast<u64*>(d_outcomes), nullptr,
                       reinterpret_cast<u64*>(d_bitmap), reinterpret_cast<u64*>(d_digests), counts, stats);
 }
 
@@ -83,11 +89,51 @@ int dc_replay_outcome(dc_ctx* c, const dc_pos* start, uint32_t start_halfmove, c
   if (bitmap) HIP_TRY(c->bitmap.ensure(std::max<size_t>(words, 1)));
   if (digests) HIP_TRY(c->digests.ensure(std::max<size_t>(n_games, 1)));
   if (nm) HIP_TRY(hipMemcpyAsync(c->moves.p, moves, nm * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-  const int r = outcome_impl(c, start, start_halfmove, c->moves.p, n_games, n_plies, c->outcomes.p,
+  const int r = outcome_impl(c, start, start_halfmove, c->moves.p, n_games, n_plies, c->outcomes.p, nullptr,
                              bitmap ? c->bitmap.p : nullptr, digests ? c->digests.p : nullptr, counts, stats);
   if (r != DC_SUCCESS) return r;
   if (n_games)
     HIP_TRY(hipMemcpyAsync(outcomes, c->outcomes.p, (size_t)n_games * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (bitmap && words)
+    HIP_TRY(hipMemcpyAsync(bitmap, c->bitmap.p, words * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (digests && n_games)
+    HIP_TRY(hipMemcpyAsync(digests, c->digests.p, (size_t)n_games * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  return sync_ctx(c);
+}
+
+// dc_replay_outcome* with the SAN byte of every ply (k_replay_san).
+int dc_replay_san_device(dc_ctx* c, const dc_pos* start, uint32_t start_halfmove, const uint16_t* d_moves,
+                         uint32_t n_games, uint32_t n_plies, void* d_outcomes, uint8_t* d_san, uint64_t* d_bitmap,
+                         uint64_t* d_digests, uint64_t* counts, dc_replay_stats* stats) {
+  ENTER_WORK(c);
+  if ((n_games && n_plies && (!d_moves || !d_san)) || (n_games && !d_outcomes)) return DC_EINVAL;
+  if (!d_san) {  // no plies: nothing is stored, the pointer only selects the kernel
+    HIP_TRY(c->san.ensure(1));
+    d_san = c->san.p;
+  }
+  return outcome_impl(c, start, start_halfmove, d_moves, n_games, n_plies, static_cast<u64*>(d_outcomes), d_san,
+                      reinterpret_cast<u64*>(d_bitmap), reinterpret_cast<u64*>(d_digests), counts, stats);
+}
+
+int dc_replay_san(dc_ctx* c, const dc_pos* start, uint32_t start_halfmove, const uint16_t* moves, uint32_t n_games,
+                  uint32_t n_plies, void* outcomes, uint8_t* san, uint64_t* bitmap, uint64_t* digests,
+                  uint64_t* counts, dc_replay_stats* stats) {
+  ENTER_WORK(c);
+  if ((n_games && n_plies && (!moves || !san)) || (n_games && !outcomes) || start_halfmove > 150) return DC_EINVAL;
+  const size_t nm = (size_t)n_games * n_plies;
+  const size_t words = (size_t)((n_games + 63) / 64) * n_plies;
+  HIP_TRY(c->moves.ensure(std::max<size_t>(nm, 1)));
+  HIP_TRY(c->san.ensure(std::max<size_t>(nm, 1)));
+  HIP_TRY(c->outcomes.ensure(std::max<size_t>(n_games, 1)));
+  if (bitmap) HIP_TRY(c->bitmap.ensure(std::max<size_t>(words, 1)));
+  if (digests) HIP_TRY(c->digests.ensure(std::max<size_t>(n_games, 1)));
+  if (nm) HIP_TRY(hipMemcpyAsync(c->moves.p, moves, nm * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  const int r = outcome_impl(c, start, start_halfmove, c->moves.p, n_games, n_plies, c->outcomes.p, c->san.p,
+                             bitmap ? c->bitmap.p : nullptr, digests ? c->digests.p : nullptr, counts, stats);
+  if (r != DC_SUCCESS) return r;
+  if (n_games)
+    HIP_TRY(hipMemcpyAsync(outcomes, c->outcomes.p, (size_t)n_games * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (nm) HIP_TRY(hipMemcpyAsync(san, c->san.p, nm, hipMemcpyDeviceToHost, c->stream));
   if (bitmap && words)
     HIP_TRY(hipMemcpyAsync(bitmap, c->bitmap.p, words * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   if (digests && n_games)

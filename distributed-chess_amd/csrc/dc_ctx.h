@@ -248,6 +248,7 @@ struct dc_ctx {
   // dc_replay_outcome*: the position history of one chunk of games ([slot][word][game],
   // dc_outcome.hip), the block records behind their totals, the host form's outcomes
   DBuf<u64> outcome_hist, outcome_part, outcomes;
+  DBuf<uint8_t> san;  // dc_replay_san's host form: ply-major [n_plies][n_games] SAN bytes
   // games adjudicated per launch: 1 GiB of history (dc_test_outcome_chunk_games lowers it)
   u32 outcome_chunk_games = 177664;
   // the state hash's replay pre-pass is skipped past this many bytes of its

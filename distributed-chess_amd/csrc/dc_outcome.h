@@ -1,4 +1,4 @@
-// dc_outcome.h -- launch wrappers of the game-adjudication kernel (dc_outcome.hip).
+// dc_outcome.h -- launch wrappers of the game-adjudication kernels (dc_outcome.hip, dc_san.hip).
 #pragma once
 #include "dc_kernels.h"
 
@@ -24,7 +24,12 @@ inline size_t outcome_history_words(u32 games) { return (size_t)kOutcomeSlots * 
 hipError_t launch_replay_outcome(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
                                  u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
                                  u64* outcomes, u64* bitmap, u64* digests, u64* partial);
-// totals[kOutcomeRecord] = the n_blocks block records combined (xor for the digest xor).
+// The same (k_replay_san, dc_san.hip) plus san: ply-major [n_plies][n_games]
+// SAN bytes (DC_SAN_*), 0xFF where no move was made.  Same history, same records.
+hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
+                             u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
+                             u64* outcomes, uint8_t* san, u64* bitmap, u64* digests, u64* partial);
+// totals[kOutcomeRecord] =the n_blocks block records combined (xor for the digest xor).
 hipError_t launch_outcome_reduce(hipStream_t st, const u64* partial, u32 n_blocks, u64* totals);
 
 }  // namespace dc

@@ -27,6 +27,9 @@ ST_CHECK, ST_NO_MOVES, ST_DEAD = 1, 2, 4  # dc_legal_moves_batch status bits
 GO_ONGOING, GO_WHITE_WINS, GO_BLACK_WINS, GO_STALEMATE, GO_DEAD, GO_FIVEFOLD, GO_SEVENTYFIVE = range(7)
 GO_COUNT = 7
 GO_NAMES = ("ongoing", "white_wins", "black_wins", "stalemate", "dead", "fivefold", "seventyfive")
+# dc_replay_san's byte (DC_SAN_*): bits 0-2 the moved kind (KINDS order), then these flags; 0xFF = no move
+SAN_CAPTURE, SAN_FILE, SAN_RANK, SAN_CHECK, SAN_MATE = 0x08, 0x10, 0x20, 0x40, 0x80
+SAN_NONE = 0xFF
 # dc_perft_stats counters (DC_PS_*), and their names in the published tables' column order
 (PS_NODES, PS_CAPTURES, PS_EP, PS_CASTLES, PS_PROMOTIONS, PS_CHECKS, PS_DISCOVERED, PS_DOUBLE, PS_CHECKMATES,
  PS_STALEMATES, PS_KING_CAPTURES) = range(11)
@@ -110,6 +113,14 @@ def lib():
         "dc_replay_outcome_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
                                                C.POINTER(_Stats)]),
         "dc_fen_clocks": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "dc_replay_san": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                    C.POINTER(_Stats)]),
+        "dc_replay_san_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                           C.POINTER(_Stats)]),
+        "dc_san_format": (C.c_int, [C.c_uint16, C.c_uint8, _vp]),
+        "dc_pgn_movetext": (C.c_int, [_vp, _vp, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint8, C.c_uint8, _vp,
+                                      C.c_size_t, C.POINTER(C.c_size_t)]),
+        "dc_pos_to_fen": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "dc_history_append": (C.c_int, [C.c_char_p, _vp, _vp, C.c_uint32, C.c_size_t, _vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
         "dc_gen_games": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -164,6 +175,29 @@ def history_append(history, moves, info):
     buf = C.create_string_buffer(n.value + 1)
     _check(lib().dc_history_append(h, _ptr(moves), _ptr(info), len(moves), 1, buf, n.value + 1, C.byref(n)),
            "dc_history_append")
+    return buf.value.decode()
+
+
+def san_format(move, san):
+    """dc_san_format: the SAN token ('Nbd2', 'exd8=Q+', 'O-O') of one accepted
+    move from its move word and its dc_replay_san byte."""
+    buf = C.create_string_buffer(8)
+    _check(lib().dc_san_format(int(move), int(san), buf), "dc_san_format")
+    return buf.value.decode()
+
+
+def pgn_movetext(moves, san, result, first_fullmove=1, first_stm=0):
+    """dc_pgn_movetext: one game's moves and SAN bytes (1-D, one entry per ply;
+    0xFF plies are skipped) as a PGN movetext line ending in the token of
+    result (a GO_* code)."""
+    moves = np.ascontiguousarray(moves, np.uint16)
+    san = np.ascontiguousarray(san, np.uint8)
+    assert moves.shape == san.shape and moves.ndim == 1
+    n = C.c_size_t()
+    args = (_ptr(moves), _ptr(san), len(moves), 1, int(first_fullmove), int(first_stm), int(result))
+    _check(lib().dc_pgn_movetext(*args, None, 0, C.byref(n)), "dc_pgn_movetext")
+    buf = C.create_string_buffer(n.value + 1)
+    _check(lib().dc_pgn_movetext(*args, buf, n.value + 1, C.byref(n)), "dc_pgn_movetext")
     return buf.value.decode()
 
 
@@ -306,6 +340,16 @@ def fen_clocks(fen):
     hm, fm = C.c_uint32(), C.c_uint32()
     _check(lib().dc_fen_clocks(fen.encode(), C.byref(hm), C.byref(fm)), "dc_fen_clocks")
     return int(hm.value), int(fm.value)
+
+
+def pos_to_fen(pos, halfmove=0, fullmove=1):
+    """dc_pos_to_fen: the FEN of a position (the inverse of pos_from_fen + fen_clocks)."""
+    p = np.array([pos], POS_DTYPE)
+    n = C.c_size_t()
+    _check(lib().dc_pos_to_fen(_ptr(p), int(halfmove), int(fullmove), None, 0, C.byref(n)), "dc_pos_to_fen")
+    buf = C.create_string_buffer(n.value + 1)
+    _check(lib().dc_pos_to_fen(_ptr(p), int(halfmove), int(fullmove), buf, n.value + 1, C.byref(n)), "dc_pos_to_fen")
+    return buf.value.decode()
 
 
 def move_pack(fx, fy, tx, ty):
@@ -507,6 +551,37 @@ class Engine:
         _check(lib().dc_replay_outcome_device(self.ctx, _ptr(sp), int(start_halfmove), _dptr(d_moves), n_games,
                                               n_plies, _dptr(d_outcomes), _dptr(d_bitmap), _dptr(d_digests),
                                               _ptr(counts), C.byref(st)), "dc_replay_outcome_device")
+        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def replay_san(self, moves, start=None, start_halfmove=0, want_bitmap=True, want_digests=True):
+        """dc_replay_san (RULES_FIDE): replay_outcome plus the SAN byte of every
+        ply.  moves: uint16 [n_plies, n_games] ply-major.  Returns (outcomes, san
+        uint8 [n_plies, n_games], bitmap, digests, counts u64[GO_COUNT], stats dict)."""
+        moves = np.ascontiguousarray(moves, np.uint16)
+        n_plies, n_games = moves.shape
+        words = (n_games + 63) // 64
+        out = np.zeros(n_games, OUTCOME_DTYPE)
+        san = np.zeros((n_plies, n_games), np.uint8)
+        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
+        dig = np.zeros(n_games, np.uint64) if want_digests else None
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        _check(lib().dc_replay_san(self.ctx, _ptr(sp), int(start_halfmove), _ptr(moves), n_games, n_plies,
+                                   _ptr(out), _ptr(san), _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st)),
+               "dc_replay_san")
+        return out, san, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def replay_san_device(self, d_moves, n_games, n_plies, d_outcomes, d_san, d_bitmap=None, d_digests=None,
+                          start=None, start_halfmove=0):
+        """dc_replay_san_device on DeviceBuffers or raw device addresses (d_outcomes:
+        8 bytes a game, d_san: one byte a move).  Returns (counts u64[GO_COUNT], stats dict)."""
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        _check(lib().dc_replay_san_device(self.ctx, _ptr(sp), int(start_halfmove), _dptr(d_moves), n_games, n_plies,
+                                          _dptr(d_outcomes), _dptr(d_san), _dptr(d_bitmap), _dptr(d_digests),
+                                          _ptr(counts), C.byref(st)), "dc_replay_san_device")
         return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
 
     def state_hash(self, moves, names, start=None, history=""):

@@ -131,7 +131,7 @@ int dc_version(void);
  * "validate", "replay", "gen_games", "expand_count", "expand_write", "count1", "count2",
  * "legal_count" (units: positions), "legal_emit" (units: moves); beside them
  * "legal_scan", "legal_fixup" and, for batches of at most 256, "legal_small";
- * "replay_outcome" (units: moves consumed). */
+ * "replay_outcome" and "replay_san" (units: moves consumed). */
 int dc_ctx_set_profiling(dc_ctx* ctx, int enable);
 int dc_ctx_kernel_stats(dc_ctx* ctx, const char* kernel, dc_kernel_stats* out);
 int dc_ctx_reset_stats(dc_ctx* ctx);
@@ -311,6 +311,74 @@ int dc_replay_outcome_device(dc_ctx* ctx, const dc_pos* start, uint32_t start_ha
  * fields, which dc_pos_from_fen does not keep), on the host; absent fields
  * give 0 and 1.  Either output may be NULL. */
 int dc_fen_clocks(const char* fen, uint32_t* halfmove, uint32_t* fullmove);
+
+/* ------------------------------------------------- notation (SAN, PGN, FEN)
+ * dc_replay_san is dc_replay_outcome -- same arguments, same outcomes, bitmap,
+ * digests, counts and stats -- that also says what was played: san (required)
+ * is ply-major [n_plies][n_games] bytes, laid out like the moves.  It is the
+ * DC_RULES_FIDE counterpart of dc_replay_info + dc_history_append: a replica
+ * that resyncs a standard-chess move log gets its move text from one replay.
+ *
+ * The byte of an accepted ply:
+ *   bits 0-2  the moved piece's cell kind (0 P, 1 N, 2 B, 3 R, 4 Q, 5 K)
+ *   bit 3     DC_SAN_CAPTURE: the target held a piece, or en passant
+ *             (the low four bits are dc_replay_info's info)
+ *   bit 4     DC_SAN_FILE:  the origin file must be written
+ *   bit 5     DC_SAN_RANK:  the origin rank must be written
+ *   bit 6     DC_SAN_CHECK: the move leaves the opponent's king attacked
+ *   bit 7     DC_SAN_MATE:  ... and the opponent without a legal move (CHECK is set too)
+ * A rejected ply, a DC_MOVE_NONE ply and every ply at or past the game's
+ * end_ply hold 0xFF (kind 7 does not exist, so 0xFF is no move's byte).
+ * Disambiguation (FIDE C.10.3, PGN 8.2.3.4), knights, bishops, rooks and queens
+ * only: let `others` be the other pieces of the mover's kind and colour that
+ * can LEGALLY move to the same square -- a pinned piece whose move would leave
+ * its pin line does not count, and no pinned piece counts while its side is in
+ * check.  None: neither flag.  None of them on the mover's file: FILE.  Else
+ * none of them on the mover's rank: RANK.  Else both.  Pawns and kings never
+ * carry the flags (the formatter writes a capturing pawn's file by rule).
+ * CHECK and MATE are the adjudication of the position the move leads to, which
+ * the replay makes anyway.
+ * Kernel timing name: "replay_san" (units: moves consumed).
+ * The _device form takes d_moves, d_outcomes, d_san, d_bitmap and d_digests in
+ * device memory; counts and stats stay host pointers. */
+#define DC_SAN_CAPTURE 0x08u
+#define DC_SAN_FILE    0x10u
+#define DC_SAN_RANK    0x20u
+#define DC_SAN_CHECK   0x40u
+#define DC_SAN_MATE    0x80u
+int dc_replay_san(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, const uint16_t* moves,
+                  uint32_t n_games, uint32_t n_plies, void* outcomes, uint8_t* san, uint64_t* bitmap,
+                  uint64_t* digests, uint64_t* counts, dc_replay_stats* stats);
+int dc_replay_san_device(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, const uint16_t* d_moves,
+                         uint32_t n_games, uint32_t n_plies, void* d_outcomes, uint8_t* d_san, uint64_t* d_bitmap,
+                         uint64_t* d_digests, uint64_t* counts, dc_replay_stats* stats);
+/* The SAN token of one accepted move, on the host: out receives at most 7
+ * characters and the NUL.  Piece letter (none for a pawn), origin file and
+ * rank as the flags say, "x" for a capture, the target square; a capturing
+ * pawn writes its file ("exd5", en passant too, no suffix); "=N" / "=B" / "=R"
+ * / "=Q" from the move word's promo field; "O-O" / "O-O-O" for a king move of
+ * two files; then "#" if MATE, else "+" if CHECK.  DC_EINVAL for san = 0xFF, a
+ * kind above 5, a move with DC_MOVE_OOR, or a promo field that does not fit the
+ * kind (any on a piece, above 4, or a pawn reaching the last rank without). */
+int dc_san_format(uint16_t move, uint8_t san, char out[8]);
+/* The PGN movetext of one game, on the host, as one line with single spaces:
+ * "1. e4 e5 2. Nf3 ... <result>".  moves/san of ply p at [p * stride] (stride =
+ * n_games for a column of dc_replay_san's arrays); plies whose byte is 0xFF
+ * are skipped.  The first written move is numbered first_fullmove and made by
+ * first_stm (0 White, 1 Black: the line then begins "N... ").  The line ends
+ * with the token of result (a DC_GO_* code): "1-0", "0-1", "1/2-1/2" for the
+ * four draws, "*" for DC_GO_ONGOING; a game without moves is that token alone.
+ * out, out_cap and out_len as dc_history_append's: out_cap = 0 only sizes,
+ * a capacity that is too small is DC_EINVAL. */
+int dc_pgn_movetext(const uint16_t* moves, const uint8_t* san, uint32_t n_plies, size_t stride,
+                    uint32_t first_fullmove, uint8_t first_stm, uint8_t result, char* out, size_t out_cap,
+                    size_t* out_len);
+/* The FEN of a position, on the host: the inverse of dc_pos_from_fen plus
+ * dc_fen_clocks (PGN needs it for a game that does not begin at the start
+ * position).  Sizing as above.  DC_EUNSUPPORTED if the board holds a piece of
+ * kind OTHER; DC_EINVAL for stm > 1 or ep outside -1..63. */
+int dc_pos_to_fen(const dc_pos* pos, uint32_t halfmove, uint32_t fullmove, char* out, size_t out_cap,
+                  size_t* out_len);
 
 /* Seeded synthetic games: rng = splitmix64 from seed ^ game_id;
  * per ply one draw r: (r & 0xFF) < noise_per_256 -> move (r>>8)&0xFFF, else the

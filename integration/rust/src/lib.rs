@@ -84,6 +84,11 @@ pub mod sys {
     pub const DC_GO_FIVEFOLD: u8 = 5;
     pub const DC_GO_SEVENTYFIVE: u8 = 6;
     pub const DC_GO_COUNT: usize = 7;
+    pub const DC_SAN_CAPTURE: u8 = 0x08;
+    pub const DC_SAN_FILE: u8 = 0x10;
+    pub const DC_SAN_RANK: u8 = 0x20;
+    pub const DC_SAN_CHECK: u8 = 0x40;
+    pub const DC_SAN_MATE: u8 = 0x80;
     pub const DC_PS_NODES: usize = 0;
     pub const DC_PS_CAPTURES: usize = 1;
     pub const DC_PS_EP: usize = 2;
@@ -153,6 +158,20 @@ pub mod sys {
                                         d_bitmap: *mut u64, d_digests: *mut u64, counts: *mut u64,
                                         stats: *mut dc_replay_stats) -> c_int;
         pub fn dc_fen_clocks(fen: *const c_char, halfmove: *mut u32, fullmove: *mut u32) -> c_int;
+        // notation
+        pub fn dc_replay_san(ctx: *mut dc_ctx, start: *const dc_pos, start_halfmove: u32, moves: *const u16,
+                             n_games: u32, n_plies: u32, outcomes: *mut c_void, san: *mut u8, bitmap: *mut u64,
+                             digests: *mut u64, counts: *mut u64, stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_replay_san_device(ctx: *mut dc_ctx, start: *const dc_pos, start_halfmove: u32,
+                                    d_moves: *const u16, n_games: u32, n_plies: u32, d_outcomes: *mut c_void,
+                                    d_san: *mut u8, d_bitmap: *mut u64, d_digests: *mut u64, counts: *mut u64,
+                                    stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_san_format(move_: u16, san: u8, out: *mut c_char) -> c_int;
+        pub fn dc_pgn_movetext(moves: *const u16, san: *const u8, n_plies: u32, stride: usize, first_fullmove: u32,
+                               first_stm: u8, result: u8, out: *mut c_char, out_cap: usize,
+                               out_len: *mut usize) -> c_int;
+        pub fn dc_pos_to_fen(pos: *const dc_pos, halfmove: u32, fullmove: u32, out: *mut c_char, out_cap: usize,
+                             out_len: *mut usize) -> c_int;
         pub fn dc_replay_info(ctx: *mut dc_ctx, rules: u32, start: *const dc_pos, moves: *const u16, n_games: u32,
                               n_plies: u32, bitmap: *mut u64, digests: *mut u64, info: *mut u8,
                               stats: *mut dc_replay_stats) -> c_int;
@@ -379,6 +398,27 @@ impl Engine {
         Ok((out, st))
     }
 
+    /// One game's move log under the standard rules as PGN movetext
+    /// (dc_replay_san, n_games = 1, then dc_pgn_movetext): the resync path's
+    /// move text, the FIDE counterpart of replay_info + history_append.  The
+    /// first move is numbered `first_fullmove`; the side to move is the start
+    /// position's (White for the start position).
+    pub fn replay_pgn(&self, start: Option<&sys::dc_pos>, start_halfmove: u32, first_fullmove: u32, moves: &[u16])
+                      -> Result<(sys::dc_game_outcome, String), DcError> {
+        let n_plies = u32::try_from(moves.len()).map_err(|_| DcError {
+            status: sys::DC_EINVAL, what: "dc_replay_san", text: "move log longer than u32::MAX plies".into() })?;
+        let mut out = sys::dc_game_outcome::default();
+        let mut san = vec![0xFFu8; moves.len().max(1)];
+        let sp = start.map_or(std::ptr::null(), |p| p as *const sys::dc_pos);
+        check(unsafe { sys::dc_replay_san(self.0, sp, start_halfmove, moves.as_ptr(), 1, n_plies,
+                                          &mut out as *mut sys::dc_game_outcome as *mut c_void, san.as_mut_ptr(),
+                                          std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+                                          std::ptr::null_mut()) }, "dc_replay_san")?;
+        let stm = start.map_or(0, |p| p.stm);
+        let text = pgn_movetext(moves, &san[..moves.len()], first_fullmove, stm, out.result)?;
+        Ok((out, text))
+    }
+
     /// The published perft tables' columns for one position (dc_perft_stats_shard;
     /// split_depth 1, shard 0 of 1 is the whole tree).  Returns (totals, one row
     /// of DC_PS_COUNT counters per root move, the root moves).
@@ -430,6 +470,43 @@ pub fn fen_clocks(fen: &str) -> Result<(u32, u32), DcError> {
     let (mut hm, mut fm) = (0u32, 0u32);
     check(unsafe { sys::dc_fen_clocks(f.as_ptr(), &mut hm, &mut fm) }, "dc_fen_clocks")?;
     Ok((hm, fm))
+}
+
+fn text_of(mut out: Vec<u8>, len: usize, what: &'static str) -> Result<String, DcError> {
+    out.truncate(len);
+    String::from_utf8(out).map_err(|_| DcError { status: sys::DC_EINVAL, what, text: "not UTF-8".into() })
+}
+
+/// The SAN token of one accepted move (dc_san_format, host only).
+pub fn san_format(mv: u16, san: u8) -> Result<String, DcError> {
+    let mut out = vec![0u8; 8];
+    check(unsafe { sys::dc_san_format(mv, san, out.as_mut_ptr() as *mut c_char) }, "dc_san_format")?;
+    let len = out.iter().position(|&c| c == 0).unwrap_or(7);
+    text_of(out, len, "san_format")
+}
+
+/// One game's PGN movetext from its moves and SAN bytes (dc_pgn_movetext, host only).
+pub fn pgn_movetext(moves: &[u16], san: &[u8], first_fullmove: u32, first_stm: u8, result: u8)
+                    -> Result<String, DcError> {
+    let n_plies = u32::try_from(moves.len()).ok().filter(|_| moves.len() == san.len()).ok_or_else(|| DcError {
+        status: sys::DC_EINVAL, what: "pgn_movetext", text: "length mismatch".into() })?;
+    let mut len = 0usize;
+    check(unsafe { sys::dc_pgn_movetext(moves.as_ptr(), san.as_ptr(), n_plies, 1, first_fullmove, first_stm, result,
+                                        std::ptr::null_mut(), 0, &mut len) }, "dc_pgn_movetext")?;
+    let mut out = vec![0u8; len + 1];
+    check(unsafe { sys::dc_pgn_movetext(moves.as_ptr(), san.as_ptr(), n_plies, 1, first_fullmove, first_stm, result,
+                                        out.as_mut_ptr() as *mut c_char, out.len(), &mut len) }, "dc_pgn_movetext")?;
+    text_of(out, len, "pgn_movetext")
+}
+
+/// The FEN of a position (dc_pos_to_fen, host only).
+pub fn pos_to_fen(pos: &sys::dc_pos, halfmove: u32, fullmove: u32) -> Result<String, DcError> {
+    let mut len = 0usize;
+    check(unsafe { sys::dc_pos_to_fen(pos, halfmove, fullmove, std::ptr::null_mut(), 0, &mut len) }, "dc_pos_to_fen")?;
+    let mut out = vec![0u8; len + 1];
+    check(unsafe { sys::dc_pos_to_fen(pos, halfmove, fullmove, out.as_mut_ptr() as *mut c_char, out.len(), &mut len) },
+          "dc_pos_to_fen")?;
+    text_of(out, len, "pos_to_fen")
 }
 
 /// keccak256 (alloy) of one byte string, on the host.
