@@ -2277,76 +2277,107 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
 // is flagged overflow + front_declined like any run k_front declines, and the
 // host reruns on the legacy chain.  Every claimed table slot is freed here,
 // declined run or not; the last block to finish resets the record cursor.
-__global__ __launch_bounds__(256) void k_front_fold(const FrontDedup dd, const Board* __restrict__ out,
+//
+// The kernel is a chain of three dependent, scattered loads per record
+// (record -> owner index -> total / board) and is built to run beside the
+// other context's k_front, which leaves a SIMD 32 registers and a CU 7,952 B
+// of LDS: amdgpu_num_vgpr(16) caps a wave at 32
+// registers (the attribute counts pairs), and the block's tag histogram is its
+// only LDS (2,048 B).  One record per lane and pass, 256 blocks (three passes
+// at startpos perft(7)); the boards are compared half by half so that at most
+// two halves are in registers.  (The earlier form took four records per lane
+// with each stage's loads issued together, at 110 registers.)
+// The owner and duplicate counts come from the flags alone, so the first
+// kFoldCountWaves waves of the grid count a strided share of all records each:
+// one atomic per wave of the grid on each count cost ~20 us at 2,048 waves
+// (same-line device atomics pass one request at a time).
+// LDSH = false (A/B build only): no LDS at all, which would fit beside
+// k_count3c too -- the wave's distinct root tags are peeled off one at a time,
+// each with a wave sum and one global atomic.  Measured 38-40 us against 17 us
+// at every grid from 128 to 1,024 blocks:
+// ~4,000 one-lane atomics into the two cache lines of `divide`, where the
+// histogram's flush is one 20-lane atomic per block.
+constexpr u32 kFoldGrid = 256;
+constexpr u32 kFoldCountWaves = 128;
+template <bool LDSH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(16))) void k_front_fold(const FrontDedup dd, const Board* __restrict__ out,
                                                     const Range* __restrict__ rng_out, PerftResult* __restrict__ res) {
-  __shared__ u64 hist[256];
-  __shared__ u32 cnt[2];
-  tag_hist_init(hist);
-  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+  [[maybe_unused]] __shared__ u64 hist[LDSH ? 256 : 1];
+  if constexpr (LDSH) tag_hist_init(hist);
+  const u32 lane = lane_id();
+  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const u32 n_res = dd.st->n_rec;
   const u32 n = min(n_res, dd.cap_rec);  // (past cap_rec: k_front inserted nothing for those and declined)
   const u64 tb = rng_out[0].hi - rng_out[0].lo;  // owners written (0: the run was declined)
-  u32 n_own = 0, n_dup = 0;
+  const u32 stride = gridDim.x * 256;
   bool mism = false;
-  // Four records per thread and pass, each stage's loads issued together: a
-  // record is a chain of three dependent, scattered loads (record -> owner
-  // index -> total / board), and one record per pass left the kernel waiting
-  // on that chain pass after pass.
-  constexpr u32 R = 4;
-  for (u32 base = blockIdx.x * (256 * R); base < n; base += gridDim.x * (256 * R)) {  // block-uniform
-    u32 fl[R], s[R], oi[R];
-    u64 v[R];
-    bool live[R], cmp[R];
-#pragma unroll
-    for (u32 r = 0; r < R; ++r) {
-      const u32 i = base + r * 256 + threadIdx.x;
-      live[r] = i < n;
-      fl[r] = live[r] ? dd.rec_flags[i] : (u32)kFrontRecChildless;
-      s[r] = live[r] ? dd.rec_slot[i] & dd.slot_mask : 0u;
-    }
-#pragma unroll
-    for (u32 r = 0; r < R; ++r) {
-      oi[r] = fl[r] & kFrontRecChildless ? 0u : dd.owner_index[s[r]];
-      const bool hit = !(fl[r] & kFrontRecChildless) && oi[r] < tb;
-      mism |= !(fl[r] & kFrontRecChildless) && oi[r] >= tb;
-      cmp[r] = hit && !(fl[r] & kFrontRecOwner);
-      live[r] = live[r] && hit;  // from here on: the record adds a total
-    }
-    Board ra[R], rb[R];
-#pragma unroll
-    for (u32 r = 0; r < R; ++r) {
-      v[r] = live[r] ? dd.gp_total[oi[r]] : 0ull;
-      if (cmp[r]) {
-        ra[r] = load_board(dd.rec_board, base + r * 256 + threadIdx.x);
-        rb[r] = load_board(out, oi[r]);
-      }
-    }
-#pragma unroll
-    for (u32 r = 0; r < R; ++r) {
-      if (cmp[r] && !(ra[r].b0 == rb[r].b0 && ra[r].b1 == rb[r].b1 && ra[r].b2 == rb[r].b2 && ra[r].b3 == rb[r].b3)) {
+  u32 base = blockIdx.x * 256 + wave * 64;  // wave-uniform
+  for (; base < n; base += stride) {
+    const u32 i = base + lane;
+    const bool in = i < n;  // (a lane past the end: a childless non-owner, which does nothing)
+    const u32 fl = in ? dd.rec_flags[i] : (u32)kFrontRecChildless;
+    const u32 s = in ? dd.rec_slot[i] & dd.slot_mask : 0u;
+    const u32 oi = fl & kFrontRecChildless ? 0u : dd.owner_index[s];
+    const bool own = (fl & kFrontRecOwner) != 0;
+    u64 v = 0;
+    if (!(fl & kFrontRecChildless)) {
+      if (oi < tb) {
+        v = dd.gp_total[oi];
+        if (!own) {
+          const ulonglong2* a = reinterpret_cast<const ulonglong2*>(dd.rec_board + i);
+          const ulonglong2* b = reinterpret_cast<const ulonglong2*>(out + oi);
+          ulonglong2 x = a[0], y = b[0];
+          u64 d = (x.x ^ y.x) | (x.y ^ y.y);
+          x = a[1];
+          y = b[1];
+          d |= (x.x ^ y.x) | (x.y ^ y.y);
+          if (d) {
+            mism = true;
+            v = 0;
+          }
+        }
+      } else {
         mism = true;
-        v[r] = 0;
       }
-      const bool in = base + r * 256 + threadIdx.x < n;
-      if (in && (fl[r] & kFrontRecOwner)) {
-        dd.key[s[r]] = 0;
-        ++n_own;
-      } else if (in) {
-        ++n_dup;
+    }
+    if (own) dd.key[s] = 0;
+    const u32 tag = fl & 255u;
+    if constexpr (LDSH) {
+      tag_hist_add(hist, tag, v, true);
+    } else {
+      u64 m = ballot(v != 0);
+      while (m) {  // wave-uniform: one round per distinct tag
+        const int leader = lsb(m);
+        const u32 tag0 = lane_bcast(tag, (u32)leader);
+        const bool mine = v != 0 && tag == tag0;
+        const u64 sum = wave_sum64(mine ? v : 0);
+        if ((int)lane == leader) atomicAdd((unsigned long long*)(res->divide + tag0), (unsigned long long)sum);
+        m &= ~ballot(mine);
       }
-      tag_hist_add(hist, fl[r] & 255u, v[r], live[r]);
     }
   }
   if (mism) {
     res->overflow = 1;
     res->front_declined = 1;
   }
-  if (n_own) atomicAdd(&cnt[0], n_own);
-  if (n_dup) atomicAdd(&cnt[1], n_dup);
-  tag_hist_flush(hist, res->divide);  // (starts with a barrier)
+  // the owner and duplicate counts
+  const u32 gw = blockIdx.x * 4 + wave, cw = min(kFoldCountWaves, gridDim.x * 4);
+  if (gw < cw) {
+    u32 c_in = 0, c_own = 0;
+    for (u32 j = gw * 64 + lane; j < n; j += cw * 64) {
+      c_own += (dd.rec_flags[j] & kFrontRecOwner) != 0;
+      ++c_in;
+    }
+    c_in = wave_sum32(c_in);  // (n < 2^26)
+    c_own = wave_sum32(c_own);
+    if (lane == 0) {
+      if (c_own) atomicAdd((unsigned long long*)&dd.st->stats[1], (unsigned long long)c_own);
+      if (c_in - c_own) atomicAdd((unsigned long long*)&dd.st->stats[2], (unsigned long long)(c_in - c_own));
+    }
+  }
+  if constexpr (LDSH) tag_hist_flush(hist, res->divide);
+  __syncthreads();  // every wave of the block has read n_rec
   if (threadIdx.x == 0) {
-    if (cnt[0]) atomicAdd((unsigned long long*)&dd.st->stats[1], (unsigned long long)cnt[0]);
-    if (cnt[1]) atomicAdd((unsigned long long*)&dd.st->stats[2], (unsigned long long)cnt[1]);
     // every block has read n_rec before its own count here
     if (atomicAdd(&dd.st->done, 1u) == gridDim.x - 1) {
       dd.st->stats[0] = n_res;
@@ -2593,25 +2624,28 @@ hipError_t launch_set_result_cursor(hipStream_t st, ResultCursor* cur, u64* base
   return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_copy_result(const PerftResult* __restrict__ r, ResultCursor* __restrict__ cur) {
-  __shared__ u64 ws[4];
-  const ResultCursor rc = *cur;  // every thread reads it before thread 0 advances it
+// One wave, four entries per lane, the total from a wave sum: no LDS and 64
+// threads, so the launch starts on a CU that another context's kernel has
+// filled to its LDS limit.
+__global__ __launch_bounds__(64) void k_copy_result(const PerftResult* __restrict__ r, ResultCursor* __restrict__ cur) {
+  const ResultCursor rc = *cur;  // every lane reads it before lane 0 advances it (one wave: program order)
   u64* __restrict__ out = rc.base + 258 * (u64)rc.idx;
-  const u32 i = threadIdx.x, nr = r->n_root;
-  const u64 v = i < nr ? r->divide[i] : 0;
-  out[i] = v;
-  const u64 s = wave_sum64(v);
-  if (lane_id() == 0) ws[i >> 6] = s;
-  __syncthreads();
-  if (i == 0) {
+  const u32 l = threadIdx.x, nr = r->n_root;
+  u64 v[4];
+#pragma unroll
+  for (u32 k = 0; k < 4; ++k) v[k] = l + 64 * k < nr ? r->divide[l + 64 * k] : 0;
+#pragma unroll
+  for (u32 k = 0; k < 4; ++k) out[l + 64 * k] = v[k];
+  const u64 s = wave_sum64(v[0] + v[1] + v[2] + v[3]);
+  if (l == 0) {
     out[256] = (u64)nr | ((u64)r->overflow << 32);
-    out[257] = ws[0] + ws[1] + ws[2] + ws[3];
-    cur->idx = rc.idx + rc.stride;  // after the barrier: all threads hold rc
+    out[257] = s;
+    cur->idx = rc.idx + rc.stride;
   }
 }
 
 hipError_t launch_copy_result(hipStream_t st, const PerftResult* res, ResultCursor* cur) {
-  hipLaunchKernelGGL(k_copy_result, dim3(1), dim3(256), 0, st, res, cur);
+  hipLaunchKernelGGL(k_copy_result, dim3(1), dim3(64), 0, st, res, cur);
   return hipGetLastError();
 }
 
@@ -2851,7 +2885,24 @@ hipError_t launch_front(hipStream_t st, int stm0, u32 depth, const Board* root, 
 hipError_t launch_front_fold(hipStream_t st, const FrontDedup& dd, const Board* out, const Range* rng_out,
                              PerftResult* res) {
   // (a fixed grid: the record count is on the device; ~200k records at startpos perft(7))
-  hipLaunchKernelGGL(k_front_fold, dim3(256), dim3(256), 0, st, dd, out, rng_out, res);
+  u32 grid = kFoldGrid;
+#ifdef DC_AB_KNOBS
+  // DC_FOLD_GRID=N: the grid; DC_FOLD_LDS=0: the form without LDS
+  static const int ab_grid = [] {
+    const char* e = ab_env("DC_FOLD_GRID");
+    return e ? std::atoi(e) : 0;
+  }();
+  static const bool ab_no_lds = [] {
+    const char* e = ab_env("DC_FOLD_LDS");
+    return e && std::atoi(e) == 0;
+  }();
+  if (ab_grid > 0) grid = (u32)ab_grid;
+  if (ab_no_lds) {
+    hipLaunchKernelGGL(k_front_fold<false>, dim3(grid), dim3(256), 0, st, dd, out, rng_out, res);
+    return hipGetLastError();
+  }
+#endif
+  hipLaunchKernelGGL(k_front_fold<true>, dim3(grid), dim3(256), 0, st, dd, out, rng_out, res);
   return hipGetLastError();
 }
 

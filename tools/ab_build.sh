@@ -8,14 +8,12 @@ set -e
 cd "$(dirname "$0")/../distributed-chess_amd"
 make -s libdchess.so
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function"
+OBJS=$(ls build/*.o | grep -v "build/dc_perft\.o")  # every other unit of the product build
 while [ $# -ge 2 ]; do
   N=$1; F=$2; shift 2
   mkdir -p build/var/$N
   ( /opt/rocm/bin/hipcc $HIPFLAGS $F -c csrc/dc_perft.hip -o build/var/$N/dc_perft.o && \
-    /opt/rocm/bin/hipcc $HIPFLAGS -shared -o build/var/$N/libdchess.so build/var/$N/dc_perft.o \
-      build/dc_moves.o build/dc_perft_stats.o build/dc_hash.o build/dc_txsig.o build/dc_movegen.o build/dc_outcome.o build/dc_api.o build/dc_api_validate.o \
-      build/dc_api_legal.o build/dc_api_replay.o build/dc_api_outcome.o build/dc_api_txsig.o build/dc_api_perft.o build/dc_api_multi.o \
-      build/dc_test_secp.o \
+    /opt/rocm/bin/hipcc $HIPFLAGS -shared -o build/var/$N/libdchess.so build/var/$N/dc_perft.o $OBJS \
       -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib && \
     rm -f build/var/$N/dc_perft.o && echo "built build/var/$N/libdchess.so ($F)" ) &
 done
