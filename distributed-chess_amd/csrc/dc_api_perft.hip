@@ -67,13 +67,33 @@ int read_range(dc_ctx* c, int level, u64* n) {
   return DC_SUCCESS;
 }
 
-static bool shard_contiguous() {
-  static const bool v = [] {
-    const char* e = dc::ab_env("DC_SHARD");
-    return e && std::strcmp(e, "contig") == 0;
-  }();
-  return v;
+// The experiment knobs of this driver (A/B build only: the product reads none,
+// see ab_env), read once per process.
+struct Knobs {
+  bool fused3 = dc::ab_flag("DC_FUSED3", true);         // 0: the last level is written and counted by k_count2c
+  bool front = dc::ab_flag("DC_FRONT", true);           // 0: REF perft(6) / perft(7) take the round-5 chain
+  bool graphs = dc::ab_flag("DC_GRAPH", true);          // 0: no perft graphs
+  bool fide_top3 = dc::ab_flag("DC_FIDE_TOP3", false);  // 1: the round-4 plan, three plies in the one workgroup
+  bool shard_contig = dc::ab_is("DC_SHARD", "contig");  // a rank's shard: a contiguous part, not every n-th node
+  // Which k_front shapes deduplicate their grandparents (DESIGN.md section 3.9:
+  // decided by measurement).  A mask: 1 perft(7) unsharded, 2 perft(7) shards,
+  // 4 perft(6) unsharded, 8 perft(6) shards.
+  u32 front_dedup = (u32)dc::ab_int("DC_FRONT_DEDUP", 1, 0);
+};
+const Knobs& knobs() {
+  static const Knobs k;
+  return k;
 }
+
+// One perft request, as the C ABI states it.
+struct PerftReq {
+  uint32_t rules;
+  const dc_pos* pos;
+  u32 n_pos;  // root positions expanded together (dc_perft_batch; 1 otherwise)
+  uint32_t depth, split_depth, shard, n_shards;
+  bool fide() const { return rules == DC_RULES_FIDE; }
+  bool sharded() const { return n_shards > 1; }
+};
 
 // Writes *pos into the pinned root staging block.  Copies already queued on
 // the stream (dc_perft_repeat_device returns with runs in flight, each reading
@@ -91,7 +111,7 @@ bool root_staged(const dc_ctx* c, const dc_pos* pos, u32 n) {
   return true;
 }
 
-int write_root_host(dc_ctx* c, const dc_pos* pos, u32 n = 1) {
+int write_root_host(dc_ctx* c, const dc_pos* pos, u32 n) {
   if (root_staged(c, pos, n)) return DC_SUCCESS;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(c->stream, &cs));
@@ -106,40 +126,12 @@ int write_root_host(dc_ctx* c, const dc_pos* pos, u32 n = 1) {
 }
 
 // the staged roots to the device root arrays (stream-ordered)
-int upload_roots(dc_ctx* c, u32 n, bool meta = true) {
+int upload_roots(dc_ctx* c, u32 n, bool meta) {
   HIP_TRY(hipMemcpyAsync(c->root.p, c->root_host->b, n * sizeof(Board), hipMemcpyHostToDevice, c->stream));
   if (meta)  // (REF reads no castle / ep: one graph node less per run)
     HIP_TRY(hipMemcpyAsync(c->root_meta.p, c->root_host->meta, n * sizeof(uint16_t), hipMemcpyHostToDevice,
                            c->stream));
   return DC_SUCCESS;
-}
-
-// DC_FUSED3=0 (A/B build): the last level is written and counted by k_count2c.
-static bool fused3_enabled() {
-  static const bool on = [] {
-    const char* e = dc::ab_env("DC_FUSED3");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// FIDE depth 5: the top kernel stops one ply short (DC_FIDE_TOP3=1, A/B only:
-// the round-4 plan, three plies in the one workgroup)
-static bool fide_top_short() {
-  static const bool on = [] {
-    const char* e = dc::ab_env("DC_FIDE_TOP3");
-    return !(e && e[0] == '1');
-  }();
-  return on;
-}
-
-// DC_FRONT=0 (A/B build): REF perft(6) / perft(7) take the round-5 chain.
-static bool front_enabled() {
-  static const bool on = [] {
-    const char* e = dc::ab_env("DC_FRONT");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 // The shape of one perft's launch sequence: which levels are built how, decided
@@ -162,16 +154,28 @@ constexpr u64 kTopCap[4] = {1, 256, 256 * 256, 1ull << 20};
 // split_depth, within [1, F]
 static u32 shard_level(u32 split_depth, u32 F) { return std::max<u32>(1, std::min(split_depth, F)); }
 
-static PerftShape perft_shape(uint32_t rules, uint32_t depth, uint32_t split_depth, uint32_t n_shards, bool exact) {
-  const bool fide = rules == DC_RULES_FIDE;
-  const bool sharded = n_shards > 1;
+// Plies the single-workgroup top kernel builds, of `deepest` built in all (S: the
+// level a sharded run is cut at).
+static u32 top_plies(bool fide, bool exact, u32 deepest, bool sharded, u32 S) {
+  u32 T = exact ? 1 : std::min<u32>(deepest, 3);
+  // FIDE with ply 3 the deepest (perft depth 5): that ply (Kiwipete: 97,862
+  // nodes) made inside the one workgroup was ~0.3 ms per position (rocprofv3,
+  // round 4); stopping the top kernel one ply short leaves it to the level
+  // kernels on every CU
+  if (fide && !exact && T == deepest && deepest == 3 && !knobs().fide_top3) T = deepest - 1;
+  return sharded ? std::min(T, S) : T;
+}
+
+static PerftShape perft_shape(const PerftReq& q, bool exact) {
+  const bool fide = q.fide(), sharded = q.sharded();
+  const uint32_t depth = q.depth, split_depth = q.split_depth;
   PerftShape s{};
   s.F = depth >= 3 ? depth - 2 : 1;
   // (the sliced stage indexes its grandparent level from 0: a contiguous shard
   // cut at that very level (DC_SHARD=contig, A/B build) starts elsewhere, so
   // that combination takes K4 instead)
   const bool contig_at_sliced =
-      shard_contiguous() && sharded && depth == kDfsFrontier + 4 && shard_level(split_depth, s.F) == depth - 3;
+      knobs().shard_contig && sharded && depth == kDfsFrontier + 4 && shard_level(split_depth, s.F) == depth - 3;
   s.wide = !fide && (depth == kDfsFrontier + 3 || depth == kDfsFrontier + 4) && !perft_k4_forced() &&
            !contig_at_sliced;
   s.sliced = s.wide && depth == kDfsFrontier + 4;
@@ -183,37 +187,30 @@ static PerftShape perft_shape(uint32_t rules, uint32_t depth, uint32_t split_dep
   }
   s.final_plies = depth >= 3 ? 2 : 1;
   s.S = shard_level(split_depth, s.F);
-  s.T = exact ? 1 : std::min<u32>(s.F, 3);
-  // FIDE depth 5 (F = 3): the final stage's parents (Kiwipete: 97,862) made
-  // inside the one workgroup were ~0.3 ms per position (rocprofv3, round 4);
-  // stopping the top kernel one ply short leaves them to k_make_count and
-  // k_level_write on every CU
-  if (fide && !exact && s.T == s.F && s.F == 3 && fide_top_short()) s.T = s.F - 1;
-  if (sharded) s.T = std::min(s.T, s.S);
+  s.T = top_plies(fide, exact, s.F, sharded, s.S);
   s.cap_T = kTopCap[s.T];
   // REF final stage over the last three plies (k_count3c): the level F is
   // never written; its parents' level is counted and scanned, then expanded
   // group by group inside the final stage.  Needs a level to expand (L < F)
   // that is not the shard level.
-  s.fused3 = !fide && s.Ldfs == 0 && s.final_plies == 2 && s.T < s.F && !(sharded && s.S == s.F) && fused3_enabled();
+  s.fused3 = !fide && s.Ldfs == 0 && s.final_plies == 2 && s.T < s.F && !(sharded && s.S == s.F) && knobs().fused3;
   // The target ply of k_expand_top is made on many CUs by k_make_count (it
   // replaces that level's k_level_count) when that level is counted next.
   // A rank's strided shard of that ply (round 5): the words stay whole and
   // k_make_count makes only this rank's (word shard + i x n_shards), instead
   // of the one workgroup making the whole ply as boards and k_gather_shard
   // copying the shard out of it.
-  s.shard_words = !exact && sharded && s.S == s.T && s.T >= 2 && s.T < s.F && !shard_contiguous();
+  s.shard_words = !exact && sharded && s.S == s.T && s.T >= 2 && s.T < s.F && !knobs().shard_contig;
   s.top_words = !exact && s.T >= 2 && s.T < s.F && (!(sharded && s.S == s.T) || s.shard_words);
   return s;
 }
 
 // REF perft(6) / perft(7) of one root, unsharded or a strided shard of ply 3:
 // the one-launch front end (k_front) + k_count3c.
-static bool front_eligible(uint32_t rules, uint32_t depth, uint32_t split_depth, uint32_t n_shards, u32 n_pos) {
-  if (rules != DC_RULES_REF || n_pos != 1 || (depth != 6 && depth != 7) || !front_enabled() || !fused3_enabled())
+static bool front_eligible(const PerftReq& q) {
+  if (q.rules != DC_RULES_REF || q.n_pos != 1 || (q.depth != 6 && q.depth != 7) || !knobs().front || !knobs().fused3)
     return false;
-  const u32 S = perft_shape(rules, depth, split_depth, n_shards, false).S;
-  return n_shards == 1 || (S == 3 && !shard_contiguous());
+  return !q.sharded() || (perft_shape(q, false).S == 3 && !knobs().shard_contig);
 }
 
 // The buffers every perft sequence needs, allocated before anything is enqueued.
@@ -230,21 +227,11 @@ static int perft_ensure_common(dc_ctx* c) {
   return DC_SUCCESS;
 }
 
-// Which k_front shapes deduplicate their grandparents (DESIGN.md section 3.9:
-// decided by measurement).  DC_FRONT_DEDUP (A/B build) is a mask: 1 perft(7)
-// unsharded, 2 perft(7) shards, 4 perft(6) unsharded, 8 perft(6) shards.
-static u32 front_dedup_shapes() {
-  static const u32 m = [] {
-    const char* e = dc::ab_env("DC_FRONT_DEDUP");
-    return e ? (u32)std::strtoul(e, nullptr, 0) : 1u;
-  }();
-  return m;
-}
-
 // k_front's sequence: the root upload (stage_root), k_front, k_count3c (and,
 // where the grandparents are deduplicated, k_front_fold).
-static int front_enqueue_seq(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t shard, uint32_t n_shards,
-                             bool stage_root) {
+static int front_enqueue_seq(dc_ctx* c, const PerftReq& q, bool stage_root) {
+  const dc_pos* pos = q.pos;
+  const uint32_t depth = q.depth, shard = q.shard, n_shards = q.n_shards;
   int e = perft_ensure_common(c);
   if (e != DC_SUCCESS) return e;
   HIP_TRY(c->front_st.ensure(sizeof(dc::FrontState)));
@@ -260,7 +247,7 @@ static int front_enqueue_seq(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint3
   if (e != DC_SUCCESS) return e;
   HIP_TRY(c->move_words.ensure(cap_w));
   HIP_TRY(c->front_spill.ensure(dc::front_spill_words()));
-  const bool dedup = (front_dedup_shapes() >> ((depth == 7 ? 0 : 2) + (n_shards > 1 ? 1 : 0))) & 1;
+  const bool dedup = (knobs().front_dedup >> ((depth == 7 ? 0 : 2) + (n_shards > 1 ? 1 : 0))) & 1;
   dc::FrontDedup dd{};
   if (dedup) {
     constexpr u32 kSlots = 2 * (u32)dc::kMoveWordNodesMax;  // at most cap_b owners: half full
@@ -293,7 +280,7 @@ static int front_enqueue_seq(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint3
   c->last_front_dedup = dedup;
   if (stage_root) {
     e = write_root_host(c, pos, 1);
-    if (e == DC_SUCCESS) e = upload_roots(c, 1, false);
+    if (e == DC_SUCCESS) e = upload_roots(c, 1, false);  // (REF: no meta)
     if (e != DC_SUCCESS) return e;
   }
   dc::Range* rng = c->rng.p + 8;  // [8] the grandparents, [9] the move words
@@ -320,56 +307,173 @@ static int front_enqueue_seq(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint3
 // (fd_clean_*): the next front_enqueue clears it in full, but a captured graph
 // would replay without that clear and decline run after run, so the captured
 // graphs are dropped with it.
-static int front_enqueue(dc_ctx* c, const dc_pos* pos, uint32_t depth, uint32_t shard, uint32_t n_shards,
-                         bool stage_root) {
-  const int e = front_enqueue_seq(c, pos, depth, shard, n_shards, stage_root);
+static int front_enqueue(dc_ctx* c, const PerftReq& q, bool stage_root) {
+  const int e = front_enqueue_seq(c, q, stage_root);
   if (e != DC_SUCCESS && c->fd_key.p && c->fd_clean_key != c->fd_key.p) {
     for (GraphExecHandle* ge : {&c->pgraph, &c->rgraph, &c->rgraph_batch}) ge->reset();
   }
   return e;
 }
 
+// The frontier of one run while it is built: k_expand_top to level T, then one
+// level per count_and_scan + write_next, with this rank's shard taken at level
+// S.  dc_perft and dc_perft_stats drive it; what each level's capacity is, and
+// which final stage takes over where, is theirs to decide.
+struct LevelChain {
+  dc_ctx* c;
+  const PerftReq& q;
+  bool exact;        // level sizes are read back (size_level / size_next) instead of bounded,
+  bool* host_sync;   // which sets this: the sequence then depends on data (never captured)
+  bool sharded;      // a shard of level S is taken
+  u32 S, T;
+  bool contiguous;   // the shard: a contiguous part of the level (DC_SHARD=contig) instead of every n-th node
+  bool top_words;    // level T is still k_expand_top's move words: the first count_and_scan makes it
+  bool shard_words;  // ... and makes only this rank's strided shard of it (S == T)
+  dc::TopScratch ts{};
+  u32 L = 0;   // the current level,
+  u64 nb = 0;  // the bound of its node count,
+  int buf = 0;  // and which of the ping-pong level buffers holds it
+  // Level L's counts and chunk sums live in buffer pair cb; the k_level_write
+  // that makes level L + 1 can count it into the other pair (counted: no
+  // k_level_count launch for it).
+  int cb = 0;
+  bool counted = false;
+
+  bool fide() const { return q.fide(); }
+  int stm() const { return q.pos->stm ^ (int)(L & 1); }  // the side to move at level L
+  uint16_t* meta(int b) const { return fide() ? c->meta[b].p : nullptr; }
+  DBuf<u32>& counts(int k) const { return k ? c->counts2 : c->counts; }
+  DBuf<u64>& sums(int k) const { return k ? c->chunk_sum2 : c->chunk_sum; }
+
+  // The buffers of the top (allocated before anything is enqueued) and the root
+  // upload from pinned memory (stage_root = false: the caller staged it).
+  int begin(u64 cap_T, bool stage_root, bool upload_meta) {
+    int e = perft_ensure_common(c);
+    if (e != DC_SUCCESS) return e;
+    HIP_TRY(c->top_nodes.ensure(kTopCap[1] + kTopCap[2]));
+    HIP_TRY(c->top_tags.ensure(kTopCap[1] + kTopCap[2]));
+    if (fide()) HIP_TRY(c->top_meta.ensure(kTopCap[1] + kTopCap[2]));
+    e = ensure_level(c, 0, cap_T, fide());
+    if (e != DC_SUCCESS) return e;
+    if (top_words) HIP_TRY(c->top_words.ensure(cap_T));
+    for (int k = 0; k < 2; ++k) {
+      const u64 off = k ? kTopCap[1] : 0;
+      ts.nodes[k] = c->top_nodes.p + off;
+      ts.tags[k] = c->top_tags.p + off;
+      ts.meta[k] = fide() ? c->top_meta.p + off : nullptr;
+      ts.cap[k] = kTopCap[k + 1];
+    }
+    L = T;
+    nb = cap_T;
+    if (!stage_root) return DC_SUCCESS;
+    e = write_root_host(c, q.pos, q.n_pos);
+    return e == DC_SUCCESS ? upload_roots(c, q.n_pos, upload_meta) : e;
+  }
+
+  // Level T (the result block is cleared by k_expand_top itself: its first stores).
+  int expand_top() {
+    HIP_TRY(c->timed("expand_top", 0, [&] {
+      return dc::launch_expand_top(c->stream, q.rules, c->root.p, c->root_meta.p, q.pos->stm, T, ts, c->nodes[0].p,
+                                   meta(0), c->tags[0].p, nb, c->res.p, c->rng.p + T,
+                                   top_words ? c->top_words.p : nullptr, q.n_pos);
+    }));
+    return L == S ? take_shard() : DC_SUCCESS;
+  }
+
+  // This rank's shard of level L (= S).
+  int take_shard() {
+    if (!sharded) return DC_SUCCESS;
+    if (shard_words) {  // the words stay whole: only the level's Range becomes the shard's
+      HIP_TRY(dc::launch_shard_range(c->stream, c->rng.p + L, q.shard, q.n_shards));
+      return DC_SUCCESS;
+    }
+    if (contiguous) {
+      HIP_TRY(dc::launch_slice(c->stream, c->rng.p + L, q.shard, q.n_shards));
+      return DC_SUCCESS;
+    }
+    int e = ensure_level(c, buf ^ 1, nb, fide());
+    if (e != DC_SUCCESS) return e;
+    HIP_TRY(dc::launch_gather_shard(c->stream, c->nodes[buf].p, meta(buf), c->tags[buf].p, c->rng.p + L, q.shard,
+                                    q.n_shards, c->nodes[buf ^ 1].p, meta(buf ^ 1), c->tags[buf ^ 1].p));
+    buf ^= 1;
+    return DC_SUCCESS;
+  }
+
+  // Exact mode: the real size of level L (of level L + 1, once scanned) instead of its bound.
+  int size_level() { return exact ? read_size(L, &nb) : DC_SUCCESS; }
+  int size_next(u64* n) { return exact ? read_size(L + 1, n) : DC_SUCCESS; }
+  int read_size(u32 level, u64* n) {
+    *host_sync = true;
+    return read_range(c, (int)level, n);
+  }
+
+  // Level L's counts + chunk sums, then the chunk scan into Range L + 1 (capacity
+  // cap; guard: see launch_chunk_scan).  count_next: level L + 1 will be counted
+  // by the write that makes it (its chunk sums are cleared here).
+  int count_and_scan(u64 cap, u64 guard, bool count_next) {
+    const u64 nch = std::max<u64>(dc::chunks_for(nb), 1);
+    HIP_TRY(counts(cb).ensure(std::max<u64>(nb, 1)));
+    HIP_TRY(sums(cb).ensure(nch));
+    HIP_TRY(c->chunk_base.ensure(nch));
+    const u64 nch_next = std::max<u64>(dc::chunks_for(std::min<u64>(cap, 0xFFFFFFFFull)), 1);
+    if (count_next) {
+      HIP_TRY(counts(cb ^ 1).ensure(std::max<u64>(std::min<u64>(cap, 0xFFFFFFFFull), 1)));
+      HIP_TRY(sums(cb ^ 1).ensure(nch_next));
+    }
+    if (top_words) {  // level T, left as move words by k_expand_top
+      top_words = false;
+      HIP_TRY(c->timed("expand_count", 0, [&] {
+        return dc::launch_make_count(c->stream, q.rules, stm() ^ 1, ts.nodes[T - 2], ts.meta[T - 2], ts.tags[T - 2],
+                                     c->top_words.p, c->rng.p + L, nb, c->nodes[buf].p, meta(buf), c->tags[buf].p,
+                                     counts(cb).p, sums(cb).p, shard_words ? q.shard : 0u,
+                                     shard_words ? q.n_shards : 1u);
+      }));
+    } else if (!counted) {
+      HIP_TRY(c->timed("expand_count", 0, [&] {
+        return dc::launch_level_count(c->stream, q.rules, stm(), c->nodes[buf].p, meta(buf), c->rng.p + L, nb,
+                                      counts(cb).p, sums(cb).p);
+      }));
+    }
+    HIP_TRY(c->timed("scan", 0, [&] {
+      return dc::launch_chunk_scan(c->stream, sums(cb).p, c->rng.p + L, c->chunk_base.p, c->rng.p + L + 1, cap,
+                                   c->res.p, 0, guard, count_next ? sums(cb ^ 1).p : nullptr, nch_next);
+    }));
+    return DC_SUCCESS;
+  }
+
+  // Level L + 1 (capacity cap_next) written from level L, which it replaces as
+  // the current one; the shard is taken if it is level S.
+  int write_next(u64 cap_next, bool count_next) {
+    int e = ensure_level(c, buf ^ 1, cap_next, fide());
+    if (e != DC_SUCCESS) return e;
+    HIP_TRY(c->timed("expand_write", 0, [&] {
+      return dc::launch_level_write(c->stream, q.rules, stm(), c->nodes[buf].p, meta(buf), c->tags[buf].p,
+                                    c->rng.p + L, nb, counts(cb).p, c->chunk_base.p, c->nodes[buf ^ 1].p,
+                                    meta(buf ^ 1), c->tags[buf ^ 1].p, cap_next,
+                                    count_next ? counts(cb ^ 1).p : nullptr, count_next ? sums(cb ^ 1).p : nullptr);
+    }));
+    buf ^= 1;
+    counted = count_next;
+    if (count_next) cb ^= 1;
+    ++L;
+    nb = cap_next;
+    return L == S ? take_shard() : DC_SUCCESS;
+  }
+};
+
 // Enqueues one perft on the context stream up to (not including) the result
 // copy.  *host_sync is set when a level size had to be read back on the host
 // (exact mode or a level beyond the speculative budget): such a sequence
 // depends on data and is never captured as a graph.
-int perft_enqueue(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,
-                  uint32_t shard, uint32_t n_shards, bool exact, bool* host_sync, bool stage_root = true,
-                  u32 n_pos = 1, bool front = false) {
-  if (front && !exact) return front_enqueue(c, pos, depth, shard, n_shards, stage_root);
-  const bool fide = rules == DC_RULES_FIDE;
-  const bool sharded = n_shards > 1;
-  const PerftShape sh = perft_shape(rules, depth, split_depth, n_shards, exact);
+int perft_enqueue(dc_ctx* c, const PerftReq& q, bool exact, bool front, bool stage_root, bool* host_sync) {
+  if (front && !exact) return front_enqueue(c, q, stage_root);
+  const PerftShape sh = perft_shape(q, exact);
   if (sh.Ldfs > 3) return DC_EUNSUPPORTED;
   u32 F = sh.F, Ldfs = sh.Ldfs;  // (exact mode may move both to K4 below)
-  const u32 T = sh.T, S = sh.S;
-  const int final_plies = sh.final_plies;
-  const bool wide = sh.wide, sliced = sh.sliced, fused3 = sh.fused3, shard_words = sh.shard_words;
-  bool top_words = sh.top_words;  // (until level T is made from them)
-  const u64 cap_T = sh.cap_T;
-  // buffers (allocated before anything is enqueued)
-  int e = perft_ensure_common(c);
+  const bool wide = sh.wide, sliced = sh.sliced, fused3 = sh.fused3;
+  LevelChain ch{c, q, exact, host_sync, q.sharded(), sh.S, sh.T, knobs().shard_contig, sh.top_words, sh.shard_words};
+  int e = ch.begin(sh.cap_T, stage_root, q.fide());
   if (e != DC_SUCCESS) return e;
-  HIP_TRY(c->top_nodes.ensure(kTopCap[1] + kTopCap[2]));
-  HIP_TRY(c->top_tags.ensure(kTopCap[1] + kTopCap[2]));
-  if (fide) HIP_TRY(c->top_meta.ensure(kTopCap[1] + kTopCap[2]));
-  e = ensure_level(c, 0, cap_T, fide);
-  if (e != DC_SUCCESS) return e;
-  if (top_words) HIP_TRY(c->top_words.ensure(cap_T));
-  dc::TopScratch ts;
-  for (int k = 0; k < 2; ++k) {
-    const u64 off = k ? kTopCap[1] : 0;
-    ts.nodes[k] = c->top_nodes.p + off;
-    ts.tags[k] = c->top_tags.p + off;
-    ts.meta[k] = fide ? c->top_meta.p + off : nullptr;
-    ts.cap[k] = kTopCap[k + 1];
-  }
-  // root upload from pinned memory (stage_root = false: the caller staged it)
-  if (stage_root) {
-    e = write_root_host(c, pos, n_pos);
-    if (e == DC_SUCCESS) e = upload_roots(c, n_pos, fide);
-    if (e != DC_SUCCESS) return e;
-  }
   // Capacity of level L + 1 (and the node guard of level L) in speculative
   // mode: the move-word level of the fused final stage, else a board level.
   auto spec_cap = [&](u32 lvl, u64 n_lvl, u64* guard) -> u64 {
@@ -386,143 +490,72 @@ int perft_enqueue(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, 
       return std::min(n_lvl * kBranchBound, std::min(kSpecBudget, wide_level_bytes()) / kNodeBytes);
     return std::min(n_lvl * kBranchBound, kSpecBudget / kNodeBytes);
   };
-  // the result block is cleared by k_expand_top itself (its first stores)
-  HIP_TRY(c->timed("expand_top", 0, [&] {
-    return dc::launch_expand_top(c->stream, rules, c->root.p, c->root_meta.p, pos->stm, T, ts, c->nodes[0].p,
-                                 fide ? c->meta[0].p : nullptr, c->tags[0].p, cap_T, c->res.p, c->rng.p + T,
-                                 top_words ? c->top_words.p : nullptr, n_pos);
-  }));
-  u32 L = T;
-  u64 nb = cap_T;
-  int buf = 0;
-  // This rank's shard of level S: strided (default) or contiguous (DC_SHARD=contig).
-  auto take_shard = [&]() -> int {
-    if (shard_contiguous()) {
-      HIP_TRY(dc::launch_slice(c->stream, c->rng.p + L, shard, n_shards));
-      return DC_SUCCESS;
-    }
-    int e2 = ensure_level(c, buf ^ 1, nb, fide);
-    if (e2 != DC_SUCCESS) return e2;
-    HIP_TRY(dc::launch_gather_shard(c->stream, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr, c->tags[buf].p,
-                                    c->rng.p + L, shard, n_shards, c->nodes[buf ^ 1].p,
-                                    fide ? c->meta[buf ^ 1].p : nullptr, c->tags[buf ^ 1].p));
-    buf ^= 1;
-    return DC_SUCCESS;
-  };
-  if (sharded && L == S) {
-    if (shard_words) HIP_TRY(dc::launch_shard_range(c->stream, c->rng.p + L, shard, n_shards));
-    else e = take_shard();
-    if (e != DC_SUCCESS) return e;
-  }
-  // Level L's counts and chunk sums live in buffer pair cb; the k_level_write
-  // that makes level L + 1 can count it into the other pair (counted: no
-  // k_level_count launch for it).
-  int cb = 0;
-  bool counted = false;
-  DBuf<u32>* cnt_buf[2] = {&c->counts, &c->counts2};
-  DBuf<u64>* sum_buf[2] = {&c->chunk_sum, &c->chunk_sum2};
-  // One level: counts + chunk sums, chunk scan into Range L+1 (capacity cap), then `write`.
-  // count_next: level L + 1 will be counted by the write (its chunk sums are cleared here).
-  auto count_and_scan = [&](int stm, u64 cap, int select_path, u64 guard, bool count_next) -> int {
-    const u64 nch = std::max<u64>(dc::chunks_for(nb), 1);
-    HIP_TRY(cnt_buf[cb]->ensure(std::max<u64>(nb, 1)));
-    HIP_TRY(sum_buf[cb]->ensure(nch));
-    HIP_TRY(c->chunk_base.ensure(nch));
-    const u64 nch_next = std::max<u64>(dc::chunks_for(std::min<u64>(cap, 0xFFFFFFFFull)), 1);
-    if (count_next) {
-      HIP_TRY(cnt_buf[cb ^ 1]->ensure(std::max<u64>(std::min<u64>(cap, 0xFFFFFFFFull), 1)));
-      HIP_TRY(sum_buf[cb ^ 1]->ensure(nch_next));
-    }
-    if (top_words) {  // level T, left as move words by k_expand_top
-      top_words = false;
-      HIP_TRY(c->timed("expand_count", 0, [&] {
-        return dc::launch_make_count(c->stream, rules, stm ^ 1, ts.nodes[T - 2], ts.meta[T - 2], ts.tags[T - 2],
-                                     c->top_words.p, c->rng.p + L, nb, c->nodes[buf].p,
-                                     fide ? c->meta[buf].p : nullptr, c->tags[buf].p, cnt_buf[cb]->p, sum_buf[cb]->p,
-                                     shard_words ? shard : 0u, shard_words ? n_shards : 1u);
-      }));
-    } else if (!counted) {
-      HIP_TRY(c->timed("expand_count", 0, [&] {
-        return dc::launch_level_count(c->stream, rules, stm, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
-                                      c->rng.p + L, nb, cnt_buf[cb]->p, sum_buf[cb]->p);
-      }));
-    }
-    HIP_TRY(c->timed("scan", 0, [&] {
-      return dc::launch_chunk_scan(c->stream, sum_buf[cb]->p, c->rng.p + L, c->chunk_base.p, c->rng.p + L + 1, cap,
-                                   c->res.p, select_path, guard, count_next ? sum_buf[cb ^ 1]->p : nullptr, nch_next);
+  // the fused final stage over level L's children as move words (u64 when wide)
+  auto fused_stage = [&](auto* words, const Board* nodes, const uint16_t* tags, const dc::Range* rng, u64 n_bound,
+                         const u32* counts, const u64* chunk_base, u64 cap_w, u32* counter) -> int {
+    const int stm = ch.stm();
+    HIP_TRY(c->timed("level_moves", 0, [&] {
+      return dc::launch_level_moves(c->stream, stm, nodes, rng, n_bound, counts, chunk_base, words, cap_w);
+    }));
+    c->last_final = "count2";
+    HIP_TRY(c->timed("count2", 0, [&] {
+      return dc::launch_count3c(c->stream, stm, nodes, tags, rng, rng + 1, words, c->res.p, counter);
     }));
     return DC_SUCCESS;
   };
-  while (L < F) {
-    const int stm = pos->stm ^ (L & 1);
-    if (exact) {
-      *host_sync = true;
-      e = read_range(c, L, &nb);
-      if (e != DC_SUCCESS) return e;
-    }
+  e = ch.expand_top();
+  if (e != DC_SUCCESS) return e;
+  while (ch.L < F) {
+    const u32 L = ch.L;
+    e = ch.size_level();
+    if (e != DC_SUCCESS) return e;
+    const Board* nodes = c->nodes[ch.buf].p;
+    const uint16_t* tags = c->tags[ch.buf].p;
     if (fused3 && sliced && L + 1 == F) {
       // words of the whole level are never stored: per slice of grandparents,
       // k_level_moves writes that slice's words and k_count3c counts them
-      e = count_and_scan(stm, ~0ull, 0, 0, false);
+      e = ch.count_and_scan(~0ull, 0, false);
       if (e != DC_SUCCESS) return e;
       const u64 cap_w = std::min<u64>(kSliceNodes * 256, kWideWordsMax);
       HIP_TRY(c->move_words64.ensure(cap_w));
       HIP_TRY(c->slice_rng.ensure(2));
       HIP_TRY(c->slice_ctr.ensure(1));
-      const u64 n_slices = std::max<u64>((nb + kSliceNodes - 1) / kSliceNodes, 1);
+      const u64 n_slices = std::max<u64>((ch.nb + kSliceNodes - 1) / kSliceNodes, 1);
       c->last_final = "count2";
       for (u64 k = 0; k < n_slices; ++k) {
         const u64 s0 = k * kSliceNodes;
         HIP_TRY(dc::launch_wide_slice(c->stream, c->rng.p + L, c->chunk_base.p, c->rng.p + L + 1, s0, kSliceNodes,
                                       c->slice_rng.p, c->slice_ctr.p, c->res.p, cap_w));
-        HIP_TRY(c->timed("level_moves", 0, [&] {
-          return dc::launch_level_moves(c->stream, stm, c->nodes[buf].p + s0, c->slice_rng.p, kSliceNodes,
-                                        cnt_buf[cb]->p + s0, c->chunk_base.p + dc::chunks_for(s0), c->move_words64.p,
-                                        cap_w);
-        }));
-        HIP_TRY(c->timed("count2", 0, [&] {
-          return dc::launch_count3c(c->stream, stm, c->nodes[buf].p + s0, c->tags[buf].p + s0, c->slice_rng.p,
-                                    c->slice_rng.p + 1, c->move_words64.p, c->res.p, c->slice_ctr.p);
-        }));
+        e = fused_stage(c->move_words64.p, nodes + s0, tags + s0, c->slice_rng.p, kSliceNodes,
+                        ch.counts(ch.cb).p + s0, c->chunk_base.p + dc::chunks_for(s0), cap_w, c->slice_ctr.p);
+        if (e != DC_SUCCESS) return e;
       }
       return DC_SUCCESS;
     }
-    if (fused3 && L + 1 == F && (!exact || wide || nb <= dc::kMoveWordNodesMax)) {
+    if (fused3 && L + 1 == F && (!exact || wide || ch.nb <= dc::kMoveWordNodesMax)) {
       // one u32 move word per child (u64 when wide); in speculative mode a
       // grandparent level past kMoveWordNodesMax (a word level past
       // kWideWordsMax) is flagged on the device (exact rerun)
       u64 guard = 0;
-      u64 cap_f = spec_cap(L, nb, &guard);
-      e = count_and_scan(stm, exact ? ~0ull : cap_f, 0, exact ? 0 : guard, false);
+      u64 cap_f = spec_cap(L, ch.nb, &guard);
+      e = ch.count_and_scan(exact ? ~0ull : cap_f, exact ? 0 : guard, false);
+      if (e == DC_SUCCESS) e = ch.size_next(&cap_f);
       if (e != DC_SUCCESS) return e;
-      if (exact) {
-        *host_sync = true;
-        e = read_range(c, L + 1, &cap_f);
-        if (e != DC_SUCCESS) return e;
-        if (wide && cap_f > wide_words_max()) {
-          // too many words for the fused stage: K4 from this level (ply 5)
-          Ldfs = F - L;
-          F = L;
-          break;
-        }
-        if (cap_f > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+      if (exact && wide && cap_f > wide_words_max()) {
+        // too many words for the fused stage: K4 from this level (ply 5)
+        Ldfs = F - L;
+        F = L;
+        break;
       }
-      if (wide) HIP_TRY(c->move_words64.ensure(std::max<u64>(cap_f, 1)));
-      else HIP_TRY(c->move_words.ensure(std::max<u64>(cap_f, 1)));
-      HIP_TRY(c->timed("level_moves", 0, [&] {
-        return wide ? dc::launch_level_moves(c->stream, stm, c->nodes[buf].p, c->rng.p + L, nb, cnt_buf[cb]->p,
-                                             c->chunk_base.p, c->move_words64.p, cap_f)
-                    : dc::launch_level_moves(c->stream, stm, c->nodes[buf].p, c->rng.p + L, nb, cnt_buf[cb]->p,
-                                             c->chunk_base.p, c->move_words.p, cap_f);
-      }));
-      c->last_final = "count2";
-      HIP_TRY(c->timed("count2", 0, [&] {
-        return wide ? dc::launch_count3c(c->stream, stm, c->nodes[buf].p, c->tags[buf].p, c->rng.p + L,
-                                         c->rng.p + L + 1, c->move_words64.p, c->res.p)
-                    : dc::launch_count3c(c->stream, stm, c->nodes[buf].p, c->tags[buf].p, c->rng.p + L,
-                                         c->rng.p + L + 1, c->move_words.p, c->res.p);
-      }));
-      return DC_SUCCESS;
+      if (exact && cap_f > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+      if (wide) {
+        HIP_TRY(c->move_words64.ensure(std::max<u64>(cap_f, 1)));
+        return fused_stage(c->move_words64.p, nodes, tags, c->rng.p + L, ch.nb, ch.counts(ch.cb).p, c->chunk_base.p,
+                           cap_f, nullptr);
+      }
+      HIP_TRY(c->move_words.ensure(std::max<u64>(cap_f, 1)));
+      return fused_stage(c->move_words.p, nodes, tags, c->rng.p + L, ch.nb, ch.counts(ch.cb).p, c->chunk_base.p, cap_f,
+                         nullptr);
     }
     // Speculative mode never reads a level size back: the next level gets
     // min(64 x bound, kSpecBudget) of capacity, a level past it is dropped and
@@ -531,77 +564,47 @@ int perft_enqueue(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, 
     // memory, not launches.  (Reading the ply-4 size back cost perft(7) one
     // host sync mid-run and kept it out of the graph.)
     u64 guard_unused = 0;
-    u64 cap_next = exact ? nb * kBranchBound : spec_cap(L, nb, &guard_unused);
-    const bool exact_next = exact;
+    u64 cap_next = exact ? ch.nb * kBranchBound : spec_cap(L, ch.nb, &guard_unused);
     // the write counts level L + 1 when that level is counted next (not the
     // final stage's level, not a level first cut to this rank's shard)
     // (speculative mode only: exact mode sizes the next level after the scan)
-    const bool count_next = !exact && L + 1 < F && !(sharded && L + 1 == S);
-    e = count_and_scan(stm, exact_next ? ~0ull : cap_next, 0, 0, count_next);
+    const bool count_next = !exact && L + 1 < F && !(ch.sharded && L + 1 == ch.S);
+    e = ch.count_and_scan(exact ? ~0ull : cap_next, 0, count_next);
+    if (e == DC_SUCCESS) e = ch.size_next(&cap_next);
     if (e != DC_SUCCESS) return e;
-    if (exact_next) {
-      *host_sync = true;
-      e = read_range(c, L + 1, &cap_next);
-      if (e != DC_SUCCESS) return e;
-      if (sliced && L + 2 == F && cap_next * kNodeBytes > wide_level_bytes()) {
-        // the sliced stage's grandparent level would not fit: K4 from this level
-        Ldfs = F - L;
-        F = L;
-        break;
-      }
-      if (cap_next > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+    if (exact && sliced && L + 2 == F && cap_next * kNodeBytes > wide_level_bytes()) {
+      // the sliced stage's grandparent level would not fit: K4 from this level
+      Ldfs = F - L;
+      F = L;
+      break;
     }
-    e = ensure_level(c, buf ^ 1, cap_next, fide);
+    if (exact && cap_next > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+    e = ch.write_next(cap_next, count_next);
     if (e != DC_SUCCESS) return e;
-    HIP_TRY(c->timed("expand_write", 0, [&] {
-      return dc::launch_level_write(c->stream, rules, stm, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
-                                    c->tags[buf].p, c->rng.p + L, nb, cnt_buf[cb]->p, c->chunk_base.p,
-                                    c->nodes[buf ^ 1].p, fide ? c->meta[buf ^ 1].p : nullptr, c->tags[buf ^ 1].p,
-                                    cap_next, count_next ? cnt_buf[cb ^ 1]->p : nullptr,
-                                    count_next ? sum_buf[cb ^ 1]->p : nullptr);
-    }));
-    buf ^= 1;
-    counted = count_next;
-    if (count_next) cb ^= 1;
-    ++L;
-    nb = cap_next;
-    if (sharded && L == S) {
-      e = take_shard();
-      if (e != DC_SUCCESS) return e;
-    }
   }
-  const int stm = pos->stm ^ (L & 1);
-  c->last_final = Ldfs > 0 ? "dfs" : final_plies == 2 ? "count2" : "count1";
+  const int buf = ch.buf;
+  c->last_final = Ldfs > 0 ? "dfs" : sh.final_plies == 2 ? "count2" : "count1";
   if (Ldfs > 0) {
     const u64 lanes = dc::dfs_lanes();
     if (Ldfs > 1) HIP_TRY(c->dfs_stack.ensure((size_t)(Ldfs - 1) * 7 * lanes));
     HIP_TRY(c->timed("dfs", 0, [&] {
-      return dc::launch_perft_dfs(c->stream, stm ^ (int)(Ldfs & 1), Ldfs, c->nodes[buf].p, c->tags[buf].p,
-                                  c->rng.p + L, c->res.p, Ldfs > 1 ? c->dfs_stack.p : nullptr, lanes);
+      return dc::launch_perft_dfs(c->stream, ch.stm() ^ (int)(Ldfs & 1), Ldfs, c->nodes[buf].p, c->tags[buf].p,
+                                  c->rng.p + ch.L, c->res.p, Ldfs > 1 ? c->dfs_stack.p : nullptr, lanes);
     }));
-  } else if (depth >= 2) {
-    HIP_TRY(c->timed(final_plies == 2 ? "count2" : "count1", 0, [&] {
-      return dc::launch_final(c->stream, rules, stm, final_plies, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
-                              c->tags[buf].p, c->rng.p + L, nb, c->res.p->divide, nullptr);
+  } else if (q.depth >= 2) {
+    HIP_TRY(c->timed(sh.final_plies == 2 ? "count2" : "count1", 0, [&] {
+      return dc::launch_final(c->stream, q.rules, ch.stm(), sh.final_plies, c->nodes[buf].p, ch.meta(buf),
+                              c->tags[buf].p, c->rng.p + ch.L, ch.nb, c->res.p->divide);
     }));
   }
   return DC_SUCCESS;
 }
 
-// DC_GRAPH=0 disables the perft graph (A/B).
-static bool perft_graphs_enabled() {
-  static const bool on = [] {
-    const char* e = dc::ab_env("DC_GRAPH");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // What a captured sequence depends on, with the allocation epoch as of now.
-static dc_ctx::PerftKey perft_key(uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,
-                                  uint32_t shard, uint32_t n_shards, u32 n_pos, bool front) {
-  return dc_ctx::PerftKey{rules,  depth, split_depth, shard, n_shards, (u32)pos->stm, (u32)perft_k4_forced(), n_pos,
-                          g_alloc_epoch.load(), wide_words_max(), wide_level_bytes(), front};
+static dc_ctx::PerftKey perft_key(const PerftReq& q, bool front) {
+  return dc_ctx::PerftKey{q.rules, q.depth, q.split_depth, q.shard, q.n_shards, (u32)q.pos->stm,
+                          (u32)perft_k4_forced(), q.n_pos, g_alloc_epoch.load(), wide_words_max(), wide_level_bytes(),
+                          front};
 }
 
 // Ends the capture on the context stream and instantiates the graph into *out
@@ -623,13 +626,12 @@ static bool end_capture(dc_ctx* c, uint64_t key_epoch, bool ok_so_far, hipGraphE
 // hipGraph: the 12 stream operations of a perft(7) go to the GPU as one launch,
 // which removes the per-kernel launch gaps.  The root position
 // is read from the pinned staging block when the graph runs.
-int perft_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
-              uint32_t n_shards, bool exact, dc::PerftResult* out, u32 n_pos = 1, bool front = false) {
-  const bool graphable = !exact && !c->profiling && perft_graphs_enabled();
+int perft_run(dc_ctx* c, const PerftReq& q, bool exact, bool front, dc::PerftResult* out) {
+  const bool graphable = !exact && !c->profiling && knobs().graphs;
   front = front && !exact;
-  const dc_ctx::PerftKey key = perft_key(rules, pos, depth, split_depth, shard, n_shards, n_pos, front);
+  const dc_ctx::PerftKey key = perft_key(q, front);
   if (graphable && c->pgraph && c->pkey == key) {
-    int e = write_root_host(c, pos, n_pos);
+    int e = write_root_host(c, q.pos, q.n_pos);
     if (e != DC_SUCCESS) return e;
     HIP_TRY(hipGraphLaunch(c->pgraph, c->stream));
     e = sync_ctx(c);
@@ -638,7 +640,7 @@ int perft_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint
     return DC_SUCCESS;
   }
   bool host_sync = false;
-  int e = perft_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, exact, &host_sync, true, n_pos, front);
+  int e = perft_enqueue(c, q, exact, front, true, &host_sync);
   if (e != DC_SUCCESS) return e;
   HIP_TRY(hipMemcpyAsync(c->res_host, c->res.p, sizeof(dc::PerftResult), hipMemcpyDeviceToHost, c->stream));
   e = sync_ctx(c);
@@ -653,7 +655,7 @@ int perft_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint
     return DC_SUCCESS;
   }
   bool hs = false;
-  int ce = perft_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, false, &hs, true, n_pos, front);
+  int ce = perft_enqueue(c, q, false, front, true, &hs);
   if (ce == DC_SUCCESS &&
       hipMemcpyAsync(c->res_host, c->res.p, sizeof(dc::PerftResult), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     ce = DC_EHIP;
@@ -661,11 +663,18 @@ int perft_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint
   return DC_SUCCESS;
 }
 
-int perft_impl(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
-               uint32_t n_shards, uint64_t* divide, uint16_t* root_moves, uint32_t* n_root, uint64_t* total,
-               u32 n_pos = 1, uint8_t* root_parent = nullptr) {
-  if (!pos || !total || rules > DC_RULES_FIDE || n_shards == 0 || shard >= n_shards || pos->stm > 1) return DC_EINVAL;
-  if (depth > 12) return DC_EUNSUPPORTED;
+// The request's own fields as the C ABI bounds them (every entry point checks its pointers besides).
+static int check_request(const PerftReq& q) {
+  if (!q.pos || q.rules > DC_RULES_FIDE || q.n_shards == 0 || q.shard >= q.n_shards || q.pos->stm > 1) return DC_EINVAL;
+  return q.depth > 12 ? DC_EUNSUPPORTED : DC_SUCCESS;
+}
+
+// root_parent (a batch): which root position each root move belongs to, or null
+int perft_impl(dc_ctx* c, const PerftReq& q, uint64_t* divide, uint16_t* root_moves, uint32_t* n_root,
+               uint64_t* total, uint8_t* root_parent) {
+  if (!total) return DC_EINVAL;
+  if (int bad = check_request(q)) return bad;
+  const uint32_t depth = q.depth, shard = q.shard;
   *total = 0;
   if (n_root) *n_root = 0;
   if (depth == 0) {
@@ -676,15 +685,15 @@ int perft_impl(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uin
   // the one-launch front end where eligible; a position it declines (a top
   // past its LDS bounds, a level past its capacity) takes the legacy chain,
   // and speculative capacities that overflow there the exact rerun
-  bool front = front_eligible(rules, depth, split_depth, n_shards, n_pos);
-  int e = perft_run(c, rules, pos, depth, split_depth, shard, n_shards, false, &r, n_pos, front);
+  bool front = front_eligible(q);
+  int e = perft_run(c, q, false, front, &r);
   if (e == DC_SUCCESS && front && r.overflow && r.front_declined) {
     front = false;
-    e = perft_run(c, rules, pos, depth, split_depth, shard, n_shards, false, &r, n_pos, false);
+    e = perft_run(c, q, false, false, &r);
   }
   c->last_front = front;
   c->last_exact = e == DC_SUCCESS && r.overflow;
-  if (c->last_exact) e = perft_run(c, rules, pos, depth, split_depth, shard, n_shards, true, &r, n_pos);
+  if (c->last_exact) e = perft_run(c, q, true, false, &r);
   if (e != DC_SUCCESS) return e;
   if (r.overflow) return DC_EUNSUPPORTED;  // more than 256 root moves, or a level beyond 2^32 nodes
   const u32 nr = r.n_root;
@@ -707,129 +716,64 @@ int perft_impl(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uin
 
 // ========================================================= perft statistics
 // dc_perft_stats: the frontier at ply depth - 1 is built as boards, meta and
-// tags by the legacy level chain alone (k_expand_top, then k_level_count,
-// k_chunk_scan and k_level_write per level, the shard cut at split_depth
-// included; no k_front, no move-word level, no k_count3c), and k_leaf_stats
-// classifies every move of every frontier node into the counter block
-// c->pstats.  Speculative capacities and the exact mode are perft_enqueue's.
+// tags by the LevelChain alone, its move-word top and counting write switched
+// off (k_expand_top, then k_level_count, k_chunk_scan and k_level_write per
+// level, the shard cut at split_depth included; no k_front, no move-word
+// level, no k_count3c), and k_leaf_stats classifies every move of every
+// frontier node into the counter block c->pstats.  Speculative capacities
+// (within c->stats_level_cap besides) and the exact mode are perft_enqueue's.
 constexpr size_t kStatsWords = 256 * (size_t)dc::kPsCount;
 
-int stats_enqueue(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
-                  uint32_t n_shards, bool exact) {
-  const bool fide = rules == DC_RULES_FIDE;
-  const bool sharded = n_shards > 1;
-  const u32 F = depth - 1;              // the frontier's ply; 0: the root itself (depth 1)
+int stats_enqueue(dc_ctx* c, const PerftReq& q, bool exact) {
+  const bool fide = q.fide();
+  const u32 F = q.depth - 1;            // the frontier's ply; 0: the root itself (depth 1)
   const u32 Fb = std::max<u32>(F, 1);   // the deepest ply built (ply 1 gives the root moves)
-  const u32 S = shard_level(split_depth, Fb);
-  u32 T = exact ? 1 : std::min<u32>(Fb, 3);
-  if (fide && !exact && T == Fb && Fb == 3) T = 2;  // as perft_shape: a FIDE ply 3 is made on every CU
-  if (sharded) T = std::min(T, S);
+  const u32 S = shard_level(q.split_depth, Fb);
+  const u32 T = top_plies(fide, exact, Fb, q.sharded(), S);
   // (the test knob bounds the speculative top ply as it does the levels below)
   const u64 cap_T = exact ? kTopCap[T] : std::min(kTopCap[T], c->stats_level_cap);
-  int e = perft_ensure_common(c);
-  if (e != DC_SUCCESS) return e;
   HIP_TRY(c->pstats.ensure(kStatsWords));
   if (!c->pstats_host) HIP_TRY(c->pstats_host.alloc(hipHostMallocDefault, kStatsWords * sizeof(u64)));
-  HIP_TRY(c->top_nodes.ensure(kTopCap[1] + kTopCap[2]));
-  HIP_TRY(c->top_tags.ensure(kTopCap[1] + kTopCap[2]));
-  if (fide) HIP_TRY(c->top_meta.ensure(kTopCap[1] + kTopCap[2]));
-  e = ensure_level(c, 0, cap_T, fide);
-  if (e != DC_SUCCESS) return e;
-  dc::TopScratch ts;
-  for (int k = 0; k < 2; ++k) {
-    const u64 off = k ? kTopCap[1] : 0;
-    ts.nodes[k] = c->top_nodes.p + off;
-    ts.tags[k] = c->top_tags.p + off;
-    ts.meta[k] = fide ? c->top_meta.p + off : nullptr;
-    ts.cap[k] = kTopCap[k + 1];
-  }
+  bool host_sync = false;  // (nothing here is captured)
+  // boards at every level, every n-th node as the shard; at depth 1 nothing is
+  // cut (shard 0 holds the root's moves, as dc_perft_shard's depth 1)
+  LevelChain ch{c, q, exact, &host_sync, q.sharded() && F > 0, S, T, false, false, false};
   // (the meta goes up under REF too: the device root then always equals the
   // staged one, which is what root_staged lets a later captured run assume)
-  e = write_root_host(c, pos, 1);
-  if (e == DC_SUCCESS) e = upload_roots(c, 1, true);
+  int e = ch.begin(cap_T, true, true);
   if (e != DC_SUCCESS) return e;
   HIP_TRY(hipMemsetAsync(c->pstats.p, 0, kStatsWords * sizeof(u64), c->stream));
-  HIP_TRY(c->timed("expand_top", 0, [&] {
-    return dc::launch_expand_top(c->stream, rules, c->root.p, c->root_meta.p, pos->stm, T, ts, c->nodes[0].p,
-                                 fide ? c->meta[0].p : nullptr, c->tags[0].p, cap_T, c->res.p, c->rng.p + T, nullptr,
-                                 1);
-  }));
+  e = ch.expand_top();
+  if (e != DC_SUCCESS) return e;
   if (F == 0) {
-    // depth 1: the root's own moves (shard 0 holds them all, as dc_perft_shard's depth 1)
-    if (shard != 0) return DC_SUCCESS;
+    if (q.shard != 0) return DC_SUCCESS;
     HIP_TRY(c->timed("leaf_stats", 0, [&] {
-      return dc::launch_leaf_stats(c->stream, rules, pos->stm, c->root.p, fide ? c->root_meta.p : nullptr, nullptr,
+      return dc::launch_leaf_stats(c->stream, q.rules, q.pos->stm, c->root.p, fide ? c->root_meta.p : nullptr, nullptr,
                                    nullptr, 1, c->res.p, 1, c->pstats.p);
     }));
     return DC_SUCCESS;
   }
-  u32 L = T;
-  u64 nb = cap_T;
-  int buf = 0;
-  auto take_shard = [&]() -> int {  // this rank's strided shard of level S
-    int e2 = ensure_level(c, buf ^ 1, nb, fide);
-    if (e2 != DC_SUCCESS) return e2;
-    HIP_TRY(dc::launch_gather_shard(c->stream, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr, c->tags[buf].p,
-                                    c->rng.p + L, shard, n_shards, c->nodes[buf ^ 1].p,
-                                    fide ? c->meta[buf ^ 1].p : nullptr, c->tags[buf ^ 1].p));
-    buf ^= 1;
-    return DC_SUCCESS;
-  };
-  if (sharded && L == S) {
-    e = take_shard();
+  while (ch.L < F) {
+    e = ch.size_level();
     if (e != DC_SUCCESS) return e;
-  }
-  while (L < F) {
-    const int stm = pos->stm ^ (L & 1);
-    if (exact) {
-      e = read_range(c, L, &nb);
-      if (e != DC_SUCCESS) return e;
-    }
-    u64 cap_next = std::min(std::min(nb * kBranchBound, kSpecBudget / kNodeBytes), c->stats_level_cap);
-    const u64 nch = std::max<u64>(dc::chunks_for(nb), 1);
-    HIP_TRY(c->counts.ensure(std::max<u64>(nb, 1)));
-    HIP_TRY(c->chunk_sum.ensure(nch));
-    HIP_TRY(c->chunk_base.ensure(nch));
-    HIP_TRY(c->timed("expand_count", 0, [&] {
-      return dc::launch_level_count(c->stream, rules, stm, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
-                                    c->rng.p + L, nb, c->counts.p, c->chunk_sum.p);
-    }));
-    HIP_TRY(c->timed("scan", 0, [&] {
-      return dc::launch_chunk_scan(c->stream, c->chunk_sum.p, c->rng.p + L, c->chunk_base.p, c->rng.p + L + 1,
-                                   exact ? ~0ull : cap_next, c->res.p, 0);
-    }));
-    if (exact) {
-      e = read_range(c, L + 1, &cap_next);
-      if (e != DC_SUCCESS) return e;
-      if (cap_next > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
-    }
-    e = ensure_level(c, buf ^ 1, cap_next, fide);
+    u64 cap_next = std::min(std::min(ch.nb * kBranchBound, kSpecBudget / kNodeBytes), c->stats_level_cap);
+    e = ch.count_and_scan(exact ? ~0ull : cap_next, 0, false);
+    if (e == DC_SUCCESS) e = ch.size_next(&cap_next);
     if (e != DC_SUCCESS) return e;
-    HIP_TRY(c->timed("expand_write", 0, [&] {
-      return dc::launch_level_write(c->stream, rules, stm, c->nodes[buf].p, fide ? c->meta[buf].p : nullptr,
-                                    c->tags[buf].p, c->rng.p + L, nb, c->counts.p, c->chunk_base.p,
-                                    c->nodes[buf ^ 1].p, fide ? c->meta[buf ^ 1].p : nullptr, c->tags[buf ^ 1].p,
-                                    cap_next);
-    }));
-    buf ^= 1;
-    ++L;
-    nb = cap_next;
-    if (sharded && L == S) {
-      e = take_shard();
-      if (e != DC_SUCCESS) return e;
-    }
+    if (exact && cap_next > 0xFFFFFFFFull) return DC_EUNSUPPORTED;
+    e = ch.write_next(cap_next, false);
+    if (e != DC_SUCCESS) return e;
   }
   HIP_TRY(c->timed("leaf_stats", 0, [&] {
-    return dc::launch_leaf_stats(c->stream, rules, pos->stm ^ (int)(F & 1), c->nodes[buf].p,
-                                 fide ? c->meta[buf].p : nullptr, c->tags[buf].p, c->rng.p + F, nb, c->res.p, 0,
-                                 c->pstats.p);
+    return dc::launch_leaf_stats(c->stream, q.rules, ch.stm(), c->nodes[ch.buf].p, ch.meta(ch.buf), c->tags[ch.buf].p,
+                                 c->rng.p + F, ch.nb, c->res.p, 0, c->pstats.p);
   }));
   return DC_SUCCESS;
 }
 
-int stats_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
-              uint32_t n_shards, bool exact, dc::PerftResult* out) {
-  int e = stats_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, exact);
+
+int stats_run(dc_ctx* c, const PerftReq& q, bool exact, dc::PerftResult* out) {
+  int e = stats_enqueue(c, q, exact);
   if (e != DC_SUCCESS) return e;
   HIP_TRY(hipMemcpyAsync(c->res_host, c->res.p, sizeof(dc::PerftResult), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->pstats_host, c->pstats.p, kStatsWords * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -839,20 +783,20 @@ int stats_run(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint
   return DC_SUCCESS;
 }
 
-int stats_impl(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
-               uint32_t n_shards, uint64_t* totals, uint64_t* rows, uint16_t* root_moves, uint32_t* n_root) {
-  if (!pos || !totals || rules > DC_RULES_FIDE || n_shards == 0 || shard >= n_shards || pos->stm > 1) return DC_EINVAL;
-  if (depth > 12) return DC_EUNSUPPORTED;
+int stats_impl(dc_ctx* c, const PerftReq& q, uint64_t* totals, uint64_t* rows, uint16_t* root_moves,
+               uint32_t* n_root) {
+  if (!totals) return DC_EINVAL;
+  if (int bad = check_request(q)) return bad;
   std::fill(totals, totals + DC_PS_COUNT, 0);
   if (n_root) *n_root = 0;
-  if (depth == 0) {
-    totals[DC_PS_NODES] = (shard == 0) ? 1 : 0;
+  if (q.depth == 0) {
+    totals[DC_PS_NODES] = (q.shard == 0) ? 1 : 0;
     return DC_SUCCESS;
   }
   dc::PerftResult r;
-  int e = stats_run(c, rules, pos, depth, split_depth, shard, n_shards, false, &r);
+  int e = stats_run(c, q, false, &r);
   c->last_stats_exact = e == DC_SUCCESS && r.overflow;
-  if (c->last_stats_exact) e = stats_run(c, rules, pos, depth, split_depth, shard, n_shards, true, &r);
+  if (c->last_stats_exact) e = stats_run(c, q, true, &r);
   if (e != DC_SUCCESS) return e;
   if (r.overflow) return DC_EUNSUPPORTED;  // more than 256 root moves, or a level beyond 2^32 nodes
   const u32 nr = r.n_root;
@@ -891,14 +835,14 @@ extern "C" __attribute__((visibility("default"))) int dc_test_perft_stats_last_e
 int dc_perft_stats(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint64_t* totals, uint64_t* rows,
                    uint16_t* root_moves, uint32_t* n_root) {
   ENTER_WORK(c);
-  return stats_impl(c, rules, pos, depth, 1, 0, 1, totals, rows, root_moves, n_root);
+  return stats_impl(c, PerftReq{rules, pos, 1, depth, 1, 0, 1}, totals, rows, root_moves, n_root);
 }
 
 int dc_perft_stats_shard(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,
                          uint32_t shard, uint32_t n_shards, uint64_t* totals, uint64_t* rows, uint16_t* root_moves,
                          uint32_t* n_root) {
   ENTER_WORK(c);
-  return stats_impl(c, rules, pos, depth, split_depth, shard, n_shards, totals, rows, root_moves, n_root);
+  return stats_impl(c, PerftReq{rules, pos, 1, depth, split_depth, shard, n_shards}, totals, rows, root_moves, n_root);
 }
 
 // Test hook (not in the header): 1 when the context's last perft ran the
@@ -941,13 +885,14 @@ extern "C" __attribute__((visibility("default"))) int dc_test_front_hash_mask(dc
 int dc_perft(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint64_t* divide, uint16_t* root_moves,
              uint32_t* n_root, uint64_t* total) {
   ENTER_WORK(c);
-  return perft_impl(c, rules, pos, depth, 1, 0, 1, divide, root_moves, n_root, total);
+  return perft_impl(c, PerftReq{rules, pos, 1, depth, 1, 0, 1}, divide, root_moves, n_root, total, nullptr);
 }
 
 int dc_perft_shard(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth, uint32_t shard,
                    uint32_t n_shards, uint64_t* divide, uint16_t* root_moves, uint32_t* n_root, uint64_t* total) {
   ENTER_WORK(c);
-  return perft_impl(c, rules, pos, depth, split_depth, shard, n_shards, divide, root_moves, n_root, total);
+  return perft_impl(c, PerftReq{rules, pos, 1, depth, split_depth, shard, n_shards}, divide, root_moves, n_root, total,
+                    nullptr);
 }
 
 // n_runs perfts of one position enqueued back to back on the context stream,
@@ -955,19 +900,16 @@ int dc_perft_shard(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth,
 // host round trip between runs.  The first call of a configuration runs it once
 // through perft_impl (host sync), which captures the launch sequence; later
 // runs replay that hipGraph.  Returns once the runs are enqueued.
-// n_runs runs on context c, the results at d_out + 258 (idx0 + stride i).
+// n_runs runs on context c, run i's result at d_out + 258 i.
 // Runs per batch graph of dc_perft_repeat_device (see dc_ctx::rgraph_batch).
 constexpr u32 kRepeatBatch = 8;
 
-static int repeat_runs(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t depth, uint32_t split_depth,
-                       uint32_t shard, uint32_t n_shards, uint32_t n_runs, uint64_t* d_out, u32 idx0, u32 stride,
-                       u32 n_pos = 1) {
+static int repeat_runs(dc_ctx* c, const PerftReq& q, uint32_t n_runs, uint64_t* d_out) {
   if (n_runs == 0) return DC_SUCCESS;
   HIP_TRY(c->rcur.ensure(1));  // before the key: an allocation moves the epoch
   // (a graph captured after a declined front holds the legacy chain: front false)
-  dc_ctx::PerftKey key = perft_key(rules, pos, depth, split_depth, shard, n_shards, n_pos,
-                                   front_eligible(rules, depth, split_depth, n_shards, n_pos));
-  const bool graphable = !c->profiling && perft_graphs_enabled();
+  dc_ctx::PerftKey key = perft_key(q, front_eligible(q));
+  const bool graphable = !c->profiling && knobs().graphs;
   // capture `runs` runs of the sequence back to back (the result copy is part
   // of the graph: its destination is the cursor)
   auto capture = [&](u32 runs, hipGraphExec_t* out) {
@@ -975,7 +917,7 @@ static int repeat_runs(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t de
     bool hs = false;
     int ce = DC_SUCCESS;
     for (u32 r = 0; r < runs && ce == DC_SUCCESS && !hs; ++r) {
-      ce = perft_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, false, &hs, false, n_pos, key.front);
+      ce = perft_enqueue(c, q, false, key.front, false, &hs);
       if (ce == DC_SUCCESS && dc::launch_copy_result(c->stream, c->res.p, c->rcur.p) != hipSuccess) ce = DC_EHIP;
     }
     return end_capture(c, key.epoch, ce == DC_SUCCESS && !hs, out);
@@ -984,15 +926,15 @@ static int repeat_runs(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t de
     // a plain run (host sync) sizes the buffers and stages the root; then the
     // sequence is captured without the root upload and the readback
     uint64_t total = 0;
-    int e = perft_impl(c, rules, pos, depth, split_depth, shard, n_shards, nullptr, nullptr, nullptr, &total, n_pos);
+    int e = perft_impl(c, q, nullptr, nullptr, nullptr, &total, nullptr);
     if (e != DC_SUCCESS) return e;
     if (c->last_exact) {
       // speculative capacities overflow for this configuration: exact runs
       // (one host sync per level), each result still left on the device
-      HIP_TRY(dc::launch_set_result_cursor(c->stream, c->rcur.p, reinterpret_cast<u64*>(d_out), idx0, stride));
+      HIP_TRY(dc::launch_set_result_cursor(c->stream, c->rcur.p, reinterpret_cast<u64*>(d_out), 0, 1));
       for (u32 i = 0; i < n_runs; ++i) {
         bool hs = false;
-        e = perft_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, true, &hs, true, n_pos);
+        e = perft_enqueue(c, q, true, false, true, &hs);
         if (e != DC_SUCCESS) return e;
         HIP_TRY(dc::launch_copy_result(c->stream, c->res.p, c->rcur.p));
       }
@@ -1013,15 +955,15 @@ static int repeat_runs(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t de
     }
   }
   const bool use_graph = graphable && c->rgraph && c->rkey == key;
-  if (use_graph && !root_staged(c, pos, n_pos)) {
+  if (use_graph && !root_staged(c, q.pos, q.n_pos)) {
     // every staging copies root_host to the device root, so the device root
     // holds *pos once queued work is done if root_host does; else restage
     // (write_root_host waits for the runs still queued to read the pinned block)
-    int e = write_root_host(c, pos, n_pos);
-    if (e == DC_SUCCESS) e = upload_roots(c, n_pos);
+    int e = write_root_host(c, q.pos, q.n_pos);
+    if (e == DC_SUCCESS) e = upload_roots(c, q.n_pos, true);
     if (e != DC_SUCCESS) return e;
   }
-  HIP_TRY(dc::launch_set_result_cursor(c->stream, c->rcur.p, reinterpret_cast<u64*>(d_out), idx0, stride));
+  HIP_TRY(dc::launch_set_result_cursor(c->stream, c->rcur.p, reinterpret_cast<u64*>(d_out), 0, 1));
   u32 i = 0;
   if (use_graph && n_runs >= kRepeatBatch && !c->rgraph_batch && c->rgraph) {
     // the key's one-run graph exists but no batch graph yet (an earlier call
@@ -1035,8 +977,7 @@ static int repeat_runs(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t de
       HIP_TRY(hipGraphLaunch(c->rgraph, c->stream));  // perft + result copy
     } else {
       bool host_sync = false;
-      int e = perft_enqueue(c, rules, pos, depth, split_depth, shard, n_shards, false, &host_sync, true, n_pos,
-                            key.front);
+      int e = perft_enqueue(c, q, false, key.front, true, &host_sync);
       if (e != DC_SUCCESS) return e;
       HIP_TRY(dc::launch_copy_result(c->stream, c->res.p, c->rcur.p));
     }
@@ -1054,7 +995,7 @@ int dc_perft_repeat_device(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_
   // (round 4 measured alternating the runs over a second context, so one
   // run's front end would overlap the other's final stage: 1.03 against
   // 0.53 ms per perft(7) step; not kept)
-  return repeat_runs(c, rules, pos, depth, split_depth, shard, n_shards, n_runs, d_out, 0, 1);
+  return repeat_runs(c, PerftReq{rules, pos, 1, depth, split_depth, shard, n_shards}, n_runs, d_out);
 }
 
 // A batch of root positions with the same side to move as one tree: the top
@@ -1080,7 +1021,7 @@ int dc_perft_batch(dc_ctx* c, uint32_t rules, const dc_pos* pos, uint32_t n_pos,
   uint64_t div[256], total = 0;
   uint8_t parent[256];
   uint32_t nr = 0;
-  e = perft_impl(c, rules, pos, depth, 1, 0, 1, div, root_moves, &nr, &total, n_pos, parent);
+  e = perft_impl(c, PerftReq{rules, pos, n_pos, depth, 1, 0, 1}, div, root_moves, &nr, &total, parent);
   if (e != DC_SUCCESS) return e;
   for (u32 i = 0; i < n_pos; ++i) totals[i] = 0;
   // a root move tagged with a position outside the batch can only come from a
@@ -1101,7 +1042,7 @@ int dc_perft_batch_repeat_device(dc_ctx* c, uint32_t rules, const dc_pos* pos, u
   if (e != DC_SUCCESS) return e;
   if (n_runs && !d_out) return DC_EINVAL;
   if (depth < 2) return DC_EUNSUPPORTED;
-  return repeat_runs(c, rules, pos, depth, split_depth, 0, 1, n_runs, d_out, 0, 1, n_pos);
+  return repeat_runs(c, PerftReq{rules, pos, n_pos, depth, split_depth, 0, 1}, n_runs, d_out);
 }
 
 }  // extern "C"

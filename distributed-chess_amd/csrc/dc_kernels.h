@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace dc {
 
@@ -17,6 +18,22 @@ inline const char* ab_env(const char* name) {
   (void)name;
   return nullptr;
 #endif
+}
+// The forms a knob takes (each caller keeps the value in a static: read once per process).
+// An on/off knob: a default-on one is turned off by '0' alone, a default-off one on by '1' alone.
+static inline bool ab_flag(const char* name, bool def) {
+  const char* e = ab_env(name);
+  return (e && e[0] == (def ? '0' : '1')) ? !def : def;
+}
+// A knob that selects a named variant (DC_SHARD=contig, DC_FINAL=2b).
+static inline bool ab_is(const char* name, const char* value) {
+  const char* e = ab_env(name);
+  return e && strcmp(e, value) == 0;
+}
+// A number (base as strtol's: 0 accepts 0x...), def when unset.
+static inline long ab_int(const char* name, long def, int base) {
+  const char* e = ab_env(name);
+  return e ? strtol(e, nullptr, base) : def;
 }
 
 typedef unsigned long long u64;

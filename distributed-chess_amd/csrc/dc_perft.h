@@ -15,7 +15,7 @@ struct PerftResult {
   uint16_t root_moves[256];
   u32 n_root;
   u32 overflow;
-  u32 path;        // final stage: 0 descriptor list, 1 LDS count2
+  u32 path;        // unused since k_count2 and the descriptor path went: result-block layout, kept until device code may change
   u32 next_chunk;  // k_count2c's dynamic chunk counter (zeroed with the block)
   u64 level_n[16];
   u32 dfs_next;    // k_perft_dfs's frontier cursor (zeroed with the block)
@@ -60,6 +60,7 @@ hipError_t launch_level_count(hipStream_t st, u32 rules, int stm, const Board* n
 // (next = empty), as a total beyond cap is (the move-word path's node limit).
 // zero_next != nullptr: also clears the next level's first chunk sums (at most
 // zero_max), which launch_level_write(next_sum) then accumulates.
+// select_path: always 0 (it chose between the removed k_count2 and descriptor stages); device code, so it stays for now.
 hipError_t launch_chunk_scan(hipStream_t st, const u64* chunk_sum, const Range* rng, u64* chunk_base, Range* next,
                              u64 cap, PerftResult* res, int select_path, u64 guard = 0, u64* zero_next = nullptr,
                              u64 zero_max = 0);
@@ -87,11 +88,10 @@ hipError_t launch_copy_result(hipStream_t st, const PerftResult* res, ResultCurs
 hipError_t launch_gather_shard(hipStream_t st, const Board* in, const uint16_t* in_meta, const uint16_t* in_tags,
                                Range* rng, u32 shard, u32 n_shards, Board* out, uint16_t* out_meta,
                                uint16_t* out_tags);
-// plies = 1 (k_count1) or 2: the fused last two plies through LDS, k_count2b
-// (256-parent blocks; res == nullptr) or the wave-level k_count2 (runs only
-// when res->path == 1).
+// plies = 1 (k_count1) or 2: the fused last two plies through LDS (k_count2c
+// under REF, k_count2b's 256-parent blocks under FIDE).
 hipError_t launch_final(hipStream_t st, u32 rules, int stm, int plies, const Board* nodes, const uint16_t* meta,
-                        const uint16_t* tags, const Range* rng, u64 n_bound, u64* divide, const PerftResult* res);
+                        const uint16_t* tags, const Range* rng, u64 n_bound, u64* divide);
 
 // Perft statistics (dc_perft_stats, dc_perft_stats.hip): every move of every
 // node of the frontier `rng` (ply depth - 1; stm = its side to move) is

@@ -3,21 +3,37 @@
 // A perft(d) run is one fixed launch sequence with the level sizes kept on the
 // device (Range descriptors), so the host synchronises once per run:
 //
-//   k_expand_top      one workgroup expands the root to ply T (<= 3) in block-
-//                     scanned, deterministic (parent, class, target) order and
-//                     records the root moves (the divide keys)
-//   k_level_count     K3a  children per frontier node (bulk count) + per-chunk  \  3 launches
-//                          sums (a chunk = 256 consecutive nodes = one block)   |  per level,
-//   k_chunk_scan      one workgroup scans the chunk sums -> chunk bases and   |  grid-stride,
-//                     the next level's Range (overflow flagged beyond cap)    |  n read on
-//   k_level_write     K3b  block scan of the chunk + base -> children written   /  the device
-//   k_slice           contiguous shard of a level for data-parallel runs
-//   k_count2          the last two plies fused: per wave, 64 parents' children
-//                     are compacted into LDS (wave prefix sum) and each lane
-//                     makes one child and bulk-counts its moves per round
-//   k_emit_desc +     the last two plies for small parent levels: children as
-//   k_count_desc      8-byte descriptors, then one lane per child (balanced)
-//   k_count1          the last ply alone (depth 2)
+// The kernels, by the path of the host driver (dc_api_perft.hip) that launches them:
+//
+//   the level chain (every rule set and depth; also dc_perft_stats' frontier)
+//     k_expand_top      one workgroup expands the root(s) to ply T (<= 3) in
+//                       deterministic order and records the root moves (the
+//                       divide keys); it can leave ply T as move words
+//     k_make_count      ply T from those words on every CU: made, stored, counted
+//     k_level_count     children per node + per-chunk sums (chunk = 256 nodes)
+//     k_chunk_scan      one workgroup: chunk sums -> chunk bases and the next
+//                       level's Range (overflow flagged beyond the capacity)
+//     k_level_write     the children written (and, optionally, counted)
+//   the shard of a level (dc_perft_shard)
+//     k_gather_shard    every n-th node, copied;  k_shard_range  the same over
+//                       move words, size only;  k_slice  a contiguous part (A/B)
+//   the final stage
+//     k_count1          the last ply alone (depth 2)
+//     k_count2b         the last two plies, 256 parents per block (FIDE)
+//     k_count2c         the last two plies with the bulk split (REF)
+//     k_level_moves +   REF, the last three plies: the children of level F - 1 as
+//     k_count3c         move words (u32, or u64 at perft(8) / (9)), counted two
+//                       plies down without being stored as boards
+//     k_wide_slice      perft(9): one slice of the grandparents for that pair
+//     k_perft_dfs       K4, REF past that: 1 to 3 plies walked per lane above the
+//                       two-ply count
+//   the one-launch front end (REF perft(6) / (7) of one root)
+//     k_front           root -> the final stage's grandparents and their move
+//                       words (then k_count3c), optionally deduplicated
+//     k_front_fold      after a deduplicating k_front: totals -> divide
+//   repeated runs (dc_perft_repeat_device)
+//     k_set_result_cursor, k_copy_result   a run's result kept on the device
+//
 // Writes beyond a level's capacity are dropped and flagged; the host then
 // reruns the exact (host-sized) path.  Divide counts accumulate per root move
 // with one atomic per wave.
@@ -27,11 +43,10 @@
 #include <cstdlib>
 #include <cstddef>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <type_traits>
 
 #include "dc_common.h"
+#include "dc_launch.h"
 #include "dc_perft.h"
 
 DC_BBPROF_DEFINE(perft)  // measurement builds only (tools/bbprof.py)
@@ -503,7 +518,8 @@ __global__ __launch_bounds__(256) void k_make_count(const Board* __restrict__ pa
 // the next level's Range and flags overflow beyond cap.
 // select_path != 0: instead of flagging overflow, a total beyond cap -- or a
 // parent level larger than select_path nodes -- selects the LDS count2 path
-// (res->path = 1) and leaves the descriptor range empty.
+// (res->path = 1) and leaves the descriptor range empty.  (Both of those final
+// stages are gone and every caller passes 0: see dc_perft.h.)
 __global__ __launch_bounds__(kTopThreads) void k_chunk_scan(const u64* __restrict__ chunk_sum, const Range* __restrict__ rng,
                                                              u64* __restrict__ chunk_base, Range* __restrict__ next,
                                                              u64 cap, PerftResult* __restrict__ res, int select_path,
@@ -1366,32 +1382,6 @@ __global__ __launch_bounds__(kFrontThreads) __attribute__((amdgpu_num_vgpr(60)))
   }
 }
 
-// Children of the final level as 8-byte descriptors {parent index, move}.
-template <class R, int STM>
-__global__ __launch_bounds__(256) void k_emit_desc(const Board* __restrict__ nodes, const uint16_t* __restrict__ meta,
-                                                   const Range* __restrict__ rng, const u32* __restrict__ counts,
-                                                   const u64* __restrict__ chunk_base, u64* __restrict__ desc, u64 cap,
-                                                   const PerftResult* __restrict__ res) {
-  __shared__ u64 wsum[4];
-  if (res->path != 0) return;  // count2 was selected
-  const u64 lo = rng->lo, hi = rng->hi;
-  const u64 nch = (hi - lo + kChunk - 1) / kChunk;
-  for (u64 c = blockIdx.x; c < nch; c += gridDim.x) {
-    const u64 i = lo + c * kChunk + threadIdx.x;
-    const bool valid = i < hi;
-    const u32 cnt = valid ? counts[i - lo] : 0;
-    u64 tot;
-    u64 o = block_excl_scan64<4>(cnt, wsum, &tot) + chunk_base[c];
-    if (!valid) continue;
-    const Board p = load_board(nodes, i);
-    const u32 pm = load_meta<R>(meta, i);
-    R::template for_each<STM>(p, pm, [&](int f, int t, int promo) {
-      if (o < cap) desc[o] = i | ((u64)((u32)f | ((u32)t << 6) | ((u32)promo << 12)) << 32);
-      ++o;
-    });
-  }
-}
-
 // One slice [s0, s0 + len) of the grandparent level `lvl` (lo = 0) for the
 // sliced fused final stage: out[0] = its nodes {0, n}, out[1] = its children's
 // move words {0, w} (from the level's chunk offsets; words_total = the level's
@@ -1462,84 +1452,6 @@ __global__ __launch_bounds__(256) void k_count1(const Board* __restrict__ nodes,
   }
   tag_hist_flush(hist, divide);
 }
-
-constexpr int kC2Waves = 4;
-constexpr int kC2Cap = 64 * 28;  // child slots per wave and window (4 blocks of 4 waves per CU)
-
-struct C2Shared {
-  Board parent[kC2Waves][64];
-  u32 pmeta[kC2Waves][64];
-  u32 slot[kC2Waves][kC2Cap];
-  u64 hist[256];
-};
-
-#ifdef DC_AB_KNOBS  // round-1 final stage, kept for A/B measurement only
-template <class R, int STM>
-__global__ __launch_bounds__(256, 4) void k_count2(const Board* __restrict__ nodes, const uint16_t* __restrict__ meta,
-                                                const uint16_t* __restrict__ tags, const Range* __restrict__ rng,
-                                                u64* __restrict__ divide, const PerftResult* __restrict__ res) {
-  if (res && res->path == 0) return;  // the descriptor path was selected
-  __shared__ C2Shared sh;
-  tag_hist_init(sh.hist);
-  const u32 w = threadIdx.x >> 6;
-  const u32 lane = lane_id();
-  Board* par = sh.parent[w];
-  u32* pmeta = sh.pmeta[w];
-  u32* slot = sh.slot[w];
-  const u64 lo = rng->lo, hi = rng->hi;
-  const u64 groups = (hi - lo + 63) >> 6;
-  for (u64 g = (u64)blockIdx.x * kC2Waves + w; g < groups; g += (u64)gridDim.x * kC2Waves) {
-    const u64 i = lo + (g << 6) + lane;
-    const bool valid = i < hi;
-    Board p{0, 0, 0, 0};
-    u32 tag = 0, pm = 0;
-    if (valid) {
-      p = load_board(nodes, i);
-      pm = load_meta<R>(meta, i);
-      tag = tags[i];
-    }
-    const u32 cnt = valid ? R::template count<STM>(p, pm) : 0;
-    const u32 incl = wave_incl_scan(cnt);
-    const u32 excl = incl - cnt;
-    const u32 total = __shfl(incl, 63, 64);
-    const u64 vmask = ballot(valid);
-    const u32 tag0 = __shfl(tag, lsb(vmask), 64);
-    par[lane] = p;
-    if constexpr (R::kMeta) pmeta[lane] = pm;
-    u64 acc = 0;  // grandchildren under parents whose tag == tag0
-    for (u32 base = 0; base < total; base += kC2Cap) {
-      wave_lds_sync();
-      u32 j = excl;
-      if (valid) {
-        R::template for_each<STM>(p, pm, [&](int f, int t, int promo) {
-          if (j >= base && j - base < (u32)kC2Cap && j < excl + cnt)
-            slot[j - base] = (u32)f | ((u32)t << 6) | ((u32)promo << 12) | (lane << 15);
-          ++j;
-        });
-      }
-      wave_lds_sync();
-      const u32 nslots = min((u32)kC2Cap, total - base);
-      for (u32 r = lane; r < ((nslots + 63) & ~63u); r += 64) {
-        u32 k = 0, pl = 0;
-        if (r < nslots) {
-          const u32 e = slot[r];
-          pl = e >> 15;
-          Board c = par[pl];
-          const u32 cm = R::template make<STM>(c, R::kMeta ? pmeta[pl] : 0u, (int)(e & 63), (int)((e >> 6) & 63),
-                                               (int)((e >> 12) & 7));
-          k = R::template count<1 - STM>(c, cm);
-        }
-        const u32 ptag = __shfl(tag, (int)pl, 64);
-        if (ptag == tag0) acc += k;
-        else if (k) atomicAdd((unsigned long long*)&sh.hist[ptag], (unsigned long long)k);
-      }
-    }
-    tag_hist_add(sh.hist, tag0, acc, true);
-    wave_lds_sync();
-  }
-  tag_hist_flush(sh.hist, divide);
-}
-#endif  // DC_AB_KNOBS
 
 // ---------------------------------------------------- k_count2b (final stage)
 // The last two plies, one block = 256 parents (one per lane).  Their children
@@ -2502,46 +2414,11 @@ static inline u32 grid_for(u64 n, u32 per) {
   return (u32)std::max<u64>(1, std::min<u64>(b, kMaxGrid));
 }
 
-// Grid-stride kernels get at most one resident wave of blocks (occupancy x CUs):
-// a second, partial round of statically assigned blocks is pure tail.
-template <class K>
-static u32 resident_grid(K kernel, u32 block, u32 want) {
-  static std::mutex mu;
-  static std::map<const void*, u32> cache;
-  const void* key = reinterpret_cast<const void*>(kernel);
-  u32 cap;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-      int per_cu = 0, dev = 0, cus = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block, 0) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-      it = cache.emplace(key, (u32)(per_cu * cus)).first;
-    }
-    cap = it->second;
-  }
-  return std::max<u32>(1, std::min(want, cap));
+// A runtime rule set and side to move -> f(type_tag<Rules>, integral_constant<int, stm>)
+template <class F>
+static void with_rules_stm(u32 rules, int stm, F&& f) {
+  with_rules<RefRules, FideRules>(rules, [&](auto R) { with_stm(stm, [&](auto S) { f(R, S); }); });
 }
-
-#define DC_LAUNCH_STM(KERNEL, R, grid, block, st, ...)                                                     \
-  do {                                                                                                     \
-    if (stm) {                                                                                             \
-      auto k_ = KERNEL<R, 1>;                                                                              \
-      hipLaunchKernelGGL(k_, dim3(resident_grid(k_, block, grid)), dim3(block), 0, st, __VA_ARGS__);      \
-    } else {                                                                                               \
-      auto k_ = KERNEL<R, 0>;                                                                              \
-      hipLaunchKernelGGL(k_, dim3(resident_grid(k_, block, grid)), dim3(block), 0, st, __VA_ARGS__);      \
-    }                                                                                                      \
-  } while (0)
-
-#define DC_LAUNCH_RULES_STM(KERNEL, grid, block, st, ...)                                        \
-  do {                                                                                           \
-    if (rules == 0) DC_LAUNCH_STM(KERNEL, RefRules, grid, block, st, __VA_ARGS__);              \
-    else DC_LAUNCH_STM(KERNEL, FideRules, grid, block, st, __VA_ARGS__);                        \
-  } while (0)
 
 hipError_t launch_expand_top(hipStream_t st, u32 rules, const Board* root, const uint16_t* root_meta, u32 stm0,
                              u32 target, const TopScratch& s, Board* out, uint16_t* out_meta, uint16_t* out_tags,
@@ -2553,12 +2430,11 @@ hipError_t launch_expand_top(hipStream_t st, u32 rules, const Board* root, const
     b.tags[k] = s.tags[k];
     b.cap[k] = s.cap[k];
   }
-  if (rules == 0)
-    hipLaunchKernelGGL(k_expand_top<RefRules>, dim3(1), dim3(RefRules::kTopThreads), 0, st, root, root_meta, stm0, target, b, out,
-                       out_meta, out_tags, cap_out, res, out_rng, words, n_root);
-  else
-    hipLaunchKernelGGL(k_expand_top<FideRules>, dim3(1), dim3(FideRules::kTopThreads), 0, st, root, root_meta, stm0, target, b,
+  with_rules<RefRules, FideRules>(rules, [&](auto R) {
+    using Rules = tagged<decltype(R)>;
+    hipLaunchKernelGGL(k_expand_top<Rules>, dim3(1), dim3(Rules::kTopThreads), 0, st, root, root_meta, stm0, target, b,
                        out, out_meta, out_tags, cap_out, res, out_rng, words, n_root);
+  });
   return hipGetLastError();
 }
 
@@ -2566,7 +2442,10 @@ u64 chunks_for(u64 n) { return (n + kChunk - 1) / kChunk; }
 
 hipError_t launch_level_count(hipStream_t st, u32 rules, int stm, const Board* nodes, const uint16_t* meta,
                               const Range* rng, u64 n_bound, u32* counts, u64* chunk_sum) {
-  DC_LAUNCH_RULES_STM(k_level_count, grid_for(n_bound, kChunk), 256, st, nodes, meta, rng, counts, chunk_sum);
+  with_rules_stm(rules, stm, [&](auto R, auto S) {
+    launch_resident(k_level_count<tagged<decltype(R)>, S()>, 256, grid_for(n_bound, kChunk), st, nodes, meta, rng,
+                    counts, chunk_sum);
+  });
   return hipGetLastError();
 }
 
@@ -2574,9 +2453,10 @@ hipError_t launch_make_count(hipStream_t st, u32 rules, int stm_par, const Board
                              const uint16_t* par_tags, const u32* words, const Range* rng, u64 n_bound, Board* out,
                              uint16_t* out_meta, uint16_t* out_tags, u32* counts, u64* chunk_sum, u32 wsh,
                              u32 wstride) {
-  const int stm = stm_par;
-  DC_LAUNCH_RULES_STM(k_make_count, grid_for(n_bound, kChunk), 256, st, par, par_meta, par_tags, words, rng, out,
-                      out_meta, out_tags, counts, chunk_sum, wsh, wstride);
+  with_rules_stm(rules, stm_par, [&](auto R, auto S) {
+    launch_resident(k_make_count<tagged<decltype(R)>, S()>, 256, grid_for(n_bound, kChunk), st, par, par_meta,
+                    par_tags, words, rng, out, out_meta, out_tags, counts, chunk_sum, wsh, wstride);
+  });
   return hipGetLastError();
 }
 
@@ -2602,8 +2482,10 @@ hipError_t launch_level_write(hipStream_t st, u32 rules, int stm, const Board* n
                               const uint16_t* tags, const Range* rng, u64 n_bound, const u32* counts,
                               const u64* chunk_base, Board* out, uint16_t* out_meta, uint16_t* out_tags, u64 cap,
                               u32* next_counts, u64* next_sum) {
-  DC_LAUNCH_RULES_STM(k_level_write, grid_for(n_bound, kChunk), 256, st, nodes, meta, tags, rng, counts, chunk_base,
-                      out, out_meta, out_tags, cap, next_counts, next_sum);
+  with_rules_stm(rules, stm, [&](auto R, auto S) {
+    launch_resident(k_level_write<tagged<decltype(R)>, S()>, 256, grid_for(n_bound, kChunk), st, nodes, meta, tags, rng,
+                    counts, chunk_base, out, out_meta, out_tags, cap, next_counts, next_sum);
+  });
   return hipGetLastError();
 }
 
@@ -2665,10 +2547,7 @@ hipError_t launch_slice(hipStream_t st, Range* rng, u32 shard, u32 n_shards) {
 // Final-stage selection (for A/B measurement): DC_FINAL=2b forces k_count2b
 // under REF (k_count2c: 24 child slots per parent, the best of 20/24/28).
 static int final_variant() {
-  static const int v = [] {
-    const char* e = ab_env("DC_FINAL");
-    return (e && std::strcmp(e, "2b") == 0) ? 0 : 1;
-  }();
+  static const int v = ab_is("DC_FINAL", "2b") ? 0 : 1;
   return v;
 }
 #endif
@@ -2681,22 +2560,15 @@ static void launch_count2c_cap(hipStream_t st, int stm, const Board* nodes, cons
   // chunk counter
   static_assert(offsetof(PerftResult, divide) == 0, "divide heads PerftResult");
   u32* next = &reinterpret_cast<PerftResult*>(divide)->next_chunk;
-  if (stm) {
-    auto k = k_count2c<1, CAP, PHASE, BULK, MINW>;
-    hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, divide, next);
-  } else {
-    auto k = k_count2c<0, CAP, PHASE, BULK, MINW>;
-    hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, divide, next);
-  }
+  with_stm(stm, [&](auto S) {
+    launch_resident(k_count2c<S(), CAP, PHASE, BULK, MINW>, 256, kMaxGrid, st, nodes, tags, rng, divide, next);
+  });
 }
 
 static void launch_count2c(hipStream_t st, int stm, const Board* nodes, const uint16_t* tags, const Range* rng,
                            u64* divide) {
   // DC_C2C_PHASE (A/B and timing only): 3 = no bulk split; 1, 2 = partial phases
-  static const int phase = [] {
-    const char* e = ab_env("DC_C2C_PHASE");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int phase = (int)ab_int("DC_C2C_PHASE", 0, 10);
   // DC_C2C_WAVES (A/B): minimum waves per SIMD of the launch bounds, i.e. the
   // VGPR budget.  4 (default since round 2): 128 VGPRs with 52 B/lane of
   // spills; 3: 140 VGPRs, no scratch.  perft(7) count2: 0.498-0.505 vs
@@ -2705,10 +2577,7 @@ static void launch_count2c(hipStream_t st, int stm, const Board* nodes, const ui
   // blocks per CU) measured the same, and a chunk prefetch pipeline (next
   // chunk's parents in registers across the group, next index fetched a group
   // ahead) was slower at either budget (0.542 / 0.574 ms).
-  static const int waves = [] {
-    const char* e = ab_env("DC_C2C_WAVES");
-    return e ? std::atoi(e) : 4;
-  }();
+  static const int waves = (int)ab_int("DC_C2C_WAVES", 4, 10);
 #ifdef DC_AB_KNOBS
   if (phase == 1) launch_count2c_cap<kC2cCap, 1, true>(st, stm, nodes, tags, rng, divide);
   else if (phase == 2) launch_count2c_cap<kC2cCap, 2, true>(st, stm, nodes, tags, rng, divide);
@@ -2754,22 +2623,16 @@ hipError_t launch_perft_dfs(hipStream_t st, int stm_parent, u32 L, const Board* 
                             const Range* rng, PerftResult* res, u64* stack_frames, u64 lanes) {
   const DfsStack ds{stack_frames, lanes};
   const u32 grid = (u32)(lanes / 256);
-#define DC_DFS(S, LL)                                                                                        \
-  hipLaunchKernelGGL((k_perft_dfs<S, kC2cCap, LL>), dim3(grid), dim3(256), 0, st, nodes, tags, rng, res->divide, \
-                     &res->dfs_next, ds)
-  if (L == 1) {
-    if (stm_parent) DC_DFS(1, 1);
-    else DC_DFS(0, 1);
-  } else if (L == 2) {
-    if (stm_parent) DC_DFS(1, 2);
-    else DC_DFS(0, 2);
-  } else if (L == 3) {
-    if (stm_parent) DC_DFS(1, 3);
-    else DC_DFS(0, 3);
-  } else {
-    return hipErrorNotSupported;
-  }
-#undef DC_DFS
+  auto dfs = [&](auto LL) {  // (the grid is dfs_lanes(): the stack frames are sized by it)
+    with_stm(stm_parent, [&](auto S) {
+      hipLaunchKernelGGL((k_perft_dfs<S(), kC2cCap, LL()>), dim3(grid), dim3(256), 0, st, nodes, tags, rng, res->divide,
+                         &res->dfs_next, ds);
+    });
+  };
+  if (L == 1) dfs(std::integral_constant<int, 1>{});
+  else if (L == 2) dfs(std::integral_constant<int, 2>{});
+  else if (L == 3) dfs(std::integral_constant<int, 3>{});
+  else return hipErrorNotSupported;
   return hipGetLastError();
 }
 
@@ -2777,9 +2640,10 @@ template <class W>
 static hipError_t level_moves_w(hipStream_t st, int stm, const Board* nodes, const Range* rng, u64 n_bound,
                                 const u32* counts, const u64* chunk_base, W* mw, u64 mw_cap) {
   // words beyond mw_cap are dropped (a flagged level is never read)
-  auto k = stm ? k_level_moves<1, W> : k_level_moves<0, W>;
-  hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, grid_for(std::min<u64>(n_bound, kMoveWordNodes) * 4, kChunk))),
-                     dim3(256), 0, st, nodes, rng, counts, chunk_base, mw, mw_cap);
+  with_stm(stm, [&](auto S) {
+    launch_resident(k_level_moves<S(), W>, 256, grid_for(std::min<u64>(n_bound, kMoveWordNodes) * 4, kChunk), st, nodes,
+                    rng, counts, chunk_base, mw, mw_cap);
+  });
   return hipGetLastError();
 }
 hipError_t launch_level_moves(hipStream_t st, int stm, const Board* nodes, const Range* rng, u64 n_bound,
@@ -2799,29 +2663,20 @@ static hipError_t count3c_w(hipStream_t st, int stm_g, const Board* nodes, const
                             const Range* rng_ch, const W* mw, PerftResult* res, u32* counter, FrontState* fst = nullptr,
                             u64* gp_total = nullptr) {
   u32* next = counter ? counter : &res->next_chunk;
+  auto count = [&](auto DEDUP, u64* sums) {
+    with_stm(stm_g, [&](auto S) {
+      launch_resident(k_count3c<S(), kC3cCap, kC3cMinWaves, W, DEDUP()>, 256, kMaxGrid, st, nodes, tags, rng, rng_ch, mw,
+                      sums, next, fst);
+    });
+  };
+  // after a deduplicating k_front: per-grandparent totals (tags unused; u32 words only)
   if constexpr (std::is_same_v<W, u32>) {
-    if (gp_total) {  // after a deduplicating k_front: per-grandparent totals (tags unused)
-      if (stm_g) {
-        auto k = k_count3c<1, kC3cCap, kC3cMinWaves, W, true>;
-        hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
-                           gp_total, next, fst);
-      } else {
-        auto k = k_count3c<0, kC3cCap, kC3cMinWaves, W, true>;
-        hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
-                           gp_total, next, fst);
-      }
+    if (gp_total) {
+      count(std::true_type{}, gp_total);
       return hipGetLastError();
     }
   }
-  if (stm_g) {
-    auto k = k_count3c<1, kC3cCap, kC3cMinWaves, W>;
-    hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
-                       res->divide, next, fst);
-  } else {
-    auto k = k_count3c<0, kC3cCap, kC3cMinWaves, W>;
-    hipLaunchKernelGGL(k, dim3(resident_grid(k, 256, kMaxGrid)), dim3(256), 0, st, nodes, tags, rng, rng_ch, mw,
-                       res->divide, next, fst);
-  }
+  count(std::false_type{}, res->divide);
   return hipGetLastError();
 }
 hipError_t launch_count3c(hipStream_t st, int stm_g, const Board* nodes, const uint16_t* tags, const Range* rng,
@@ -2850,35 +2705,24 @@ hipError_t launch_front(hipStream_t st, int stm0, u32 depth, const Board* root, 
                         FrontState* fst, u32* spill, const FrontDedup* dd) {
   if (depth != 6 && depth != 7) return hipErrorInvalidValue;
   // one pass of the resident grid: every block does the top once
-#define DC_FRONT(S, E, D)                                                                                     \
-  do {                                                                                                        \
-    auto k_ = k_front<S, E, D>;                                                                               \
-    hipLaunchKernelGGL(k_, dim3(resident_grid(k_, kFrontThreads, kMaxGrid)), dim3(kFrontThreads), 0, st, root,    \
-                       shard, n_shards,                                                                       \
-                       out, out_tags, cap_b, mw, cap_w, res, rng_out, fst, spill, dd);                        \
-  } while (0)
-#define DC_FRONT_D(S, E)          \
-  do {                            \
-    if (dd) DC_FRONT(S, E, true); \
-    else DC_FRONT(S, E, false);   \
-  } while (0)
+  auto front = [&](auto S, auto E, auto D) {  // E: depth 7 (one ply more); D: the dedup
+    launch_resident(k_front<S(), E(), D()>, kFrontThreads, kMaxGrid, st, root, shard, n_shards, out, out_tags, cap_b, mw,
+                    cap_w, res, rng_out, fst, spill, dd);
+  };
+  constexpr std::integral_constant<int, 0> d6{};
+  constexpr std::integral_constant<int, 1> d7{};
   if (depth == 7) {
-    if (stm0) DC_FRONT_D(1, 1);
-    else DC_FRONT_D(0, 1);
+    with_stm(stm0, [&](auto S) { with_flag(dd != nullptr, [&](auto D) { front(S, d7, D); }); });
   } else {
     // perft(6) measured slower with the dedup: its
     // instantiations exist only in the A/B build (DC_FRONT_DEDUP)
 #ifdef DC_AB_KNOBS
-    if (stm0) DC_FRONT_D(1, 0);
-    else DC_FRONT_D(0, 0);
+    with_stm(stm0, [&](auto S) { with_flag(dd != nullptr, [&](auto D) { front(S, d6, D); }); });
 #else
     if (dd) return hipErrorInvalidValue;
-    if (stm0) DC_FRONT(1, 0, false);
-    else DC_FRONT(0, 0, false);
+    with_stm(stm0, [&](auto S) { front(S, d6, std::false_type{}); });
 #endif
   }
-#undef DC_FRONT_D
-#undef DC_FRONT
   return hipGetLastError();
 }
 
@@ -2888,10 +2732,7 @@ hipError_t launch_front_fold(hipStream_t st, const FrontDedup& dd, const Board* 
   u32 grid = kFoldGrid;
 #ifdef DC_AB_KNOBS
   // DC_FOLD_GRID=N: the grid; DC_FOLD_LDS=0: the form without LDS
-  static const int ab_grid = [] {
-    const char* e = ab_env("DC_FOLD_GRID");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int ab_grid = (int)ab_int("DC_FOLD_GRID", 0, 10);
   static const bool ab_no_lds = [] {
     const char* e = ab_env("DC_FOLD_LDS");
     return e && std::atoi(e) == 0;
@@ -2907,30 +2748,33 @@ hipError_t launch_front_fold(hipStream_t st, const FrontDedup& dd, const Board* 
 }
 
 // Product: REF -> k_count2c (the bulk split), FIDE -> k_count2b<FideRules>.
-// k_count2 and k_count2b<RefRules> are compiled only into the A/B build.
+// k_count2b<RefRules> (DC_FINAL=2b) is compiled only into the A/B build.
 hipError_t launch_final(hipStream_t st, u32 rules, int stm, int plies, const Board* nodes, const uint16_t* meta,
-                        const uint16_t* tags, const Range* rng, u64 n_bound, u64* divide, const PerftResult* res) {
+                        const uint16_t* tags, const Range* rng, u64 n_bound, u64* divide) {
   // divide is the run's PerftResult.divide (its first member): k_count2b's chunk counter sits in the same block
   static_assert(offsetof(PerftResult, divide) == 0, "divide heads the result block");
   u32* next_chunk = &reinterpret_cast<PerftResult*>(divide)->next_chunk;
   if (plies == 1) {
-    DC_LAUNCH_RULES_STM(k_count1, grid_for(n_bound, 256), 256, st, nodes, meta, tags, rng, divide);
+    with_rules_stm(rules, stm, [&](auto R, auto S) {
+      launch_resident(k_count1<tagged<decltype(R)>, S()>, 256, grid_for(n_bound, 256), st, nodes, meta, tags, rng,
+                      divide);
+    });
     return hipGetLastError();
   }
+  auto count2b = [&](auto R) {
+    with_stm(stm, [&](auto S) {
+      launch_resident(k_count2b<tagged<decltype(R)>, S()>, 256, kMaxGrid, st, nodes, meta, tags, rng, divide,
+                      next_chunk);
+    });
+  };
 #ifdef DC_AB_KNOBS
-  if (res != nullptr) {
-    DC_LAUNCH_RULES_STM(k_count2, grid_for(n_bound, 64 * kC2Waves), 256, st, nodes, meta, tags, rng, divide, res);
-    return hipGetLastError();
-  }
   if (rules == 0 && final_variant() == 0) {
-    DC_LAUNCH_STM(k_count2b, RefRules, kMaxGrid, 256, st, nodes, meta, tags, rng, divide, next_chunk);
+    count2b(type_tag<RefRules>{});
     return hipGetLastError();
   }
-#else
-  (void)res;
 #endif
   if (rules == 0) launch_count2c(st, stm, nodes, tags, rng, divide);
-  else DC_LAUNCH_STM(k_count2b, FideRules, kMaxGrid, 256, st, nodes, meta, tags, rng, divide, next_chunk);
+  else count2b(type_tag<FideRules>{});
   return hipGetLastError();
 }
 

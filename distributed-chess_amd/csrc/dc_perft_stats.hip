@@ -5,7 +5,8 @@
 // k_level_count, k_chunk_scan, k_level_write); this unit holds only k_leaf_stats
 // and its launch wrapper, so the perft kernels' device code is untouched.
 //
-// Shape (k_count2's): a wave stages 64 parents in LDS, compacts their legal
+// Shape (wave-level: k_count2b's LDS compaction with a wave, not a block, as
+// the unit): a wave stages 64 parents in LDS, compacts their legal
 // moves into LDS slots at wave-scan offsets (windows of kLsCap slots), and then
 // every lane takes one (parent, move) slot per round, so the lanes stay full
 // whatever the parents' branching.  For its slot a lane reads the move's flags
@@ -20,11 +21,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 #include "../../include/dchess.h"
 #include "dc_common.h"
+#include "dc_launch.h"
 #include "dc_perft.h"
 
 namespace dc {
@@ -192,46 +192,20 @@ __global__ __launch_bounds__(64 * kLsWaves, R::kMinBlocks) void k_leaf_stats(
   }
 }
 
-// One resident wave of blocks at most (the kernel strides over the groups).
-template <class K>
-u32 resident_blocks(K kernel, u32 block) {
-  static std::mutex mu;
-  static std::map<const void*, u32> cache;
-  const void* key = reinterpret_cast<const void*>(kernel);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(key);
-  if (it == cache.end()) {
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block, 0) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    it = cache.emplace(key, (u32)(per_cu * cus)).first;
-  }
-  return it->second;
-}
-
-template <class R, int STM>
-void launch_ls(hipStream_t st, const Board* nodes, const uint16_t* meta, const uint16_t* tags, const Range* rng,
-               u64 n_bound, const PerftResult* res, u32 root, u64* stats) {
-  auto k = k_leaf_stats<R, STM>;
-  const u64 want = std::max<u64>(1, (n_bound + 64 * kLsWaves - 1) / (64 * kLsWaves));
-  const u32 grid = (u32)std::min<u64>(want, resident_blocks(k, 64 * kLsWaves));
-  hipLaunchKernelGGL(k, dim3(grid), dim3(64 * kLsWaves), 0, st, nodes, meta, tags, rng, res, root, stats);
-}
-
 }  // namespace
 
 hipError_t launch_leaf_stats(hipStream_t st, u32 rules, int stm, const Board* nodes, const uint16_t* meta,
                              const uint16_t* tags, const Range* rng, u64 n_bound, const PerftResult* res, u32 root,
                              u64* stats) {
-  if (rules == 0) {
-    if (stm) launch_ls<StatsRefRules, 1>(st, nodes, meta, tags, rng, n_bound, res, root, stats);
-    else launch_ls<StatsRefRules, 0>(st, nodes, meta, tags, rng, n_bound, res, root, stats);
-  } else {
-    if (stm) launch_ls<StatsFideRules, 1>(st, nodes, meta, tags, rng, n_bound, res, root, stats);
-    else launch_ls<StatsFideRules, 0>(st, nodes, meta, tags, rng, n_bound, res, root, stats);
-  }
+  // one resident wave of blocks at most (the kernel strides over the groups)
+  constexpr u32 kBlock = 64 * kLsWaves;
+  const u32 want = (u32)std::min<u64>(std::max<u64>(1, (n_bound + kBlock - 1) / kBlock), 0xFFFFFFFFull);
+  with_rules<StatsRefRules, StatsFideRules>(rules, [&](auto R) {
+    with_stm(stm, [&](auto S) {
+      launch_resident(k_leaf_stats<tagged<decltype(R)>, S()>, kBlock, want, st, nodes, meta, tags, rng, res, root,
+                      stats);
+    });
+  });
   return hipGetLastError();
 }
 
