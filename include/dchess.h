@@ -220,7 +220,13 @@ int dc_live_validator(dc_ctx* ctx, uint32_t lease_us);
  * Replays n_games games of n_plies ply-major moves (moves[ply*n_games + g])
  * from *start (NULL = startpos).  Per ply: verdict; apply only if accepted
  * (core/src/consensus/hotstuff.rs:52-56).  bitmap (optional) is ply-major
- * [n_plies][ceil(n_games/64)] of accept bits; digests (optional) [n_games]. */
+ * [n_plies][ceil(n_games/64)] of accept bits (bits past the last game are 0);
+ * digests (optional) [n_games] are the final-state digests.  A digest covers
+ * the piece placement and the side to move, not the castling rights or the
+ * en-passant square (DC_RULES_FIDE): two games that differ only in those have
+ * equal digests, and differ in the accept bits of their later moves.  A
+ * DC_MOVE_NONE ply is skipped: not counted, and the turn does not flip; a
+ * flagged word (bit 15) counts as validated and rejected. */
 int dc_replay(dc_ctx* ctx, uint32_t rules, const dc_pos* start, const uint16_t* moves, uint32_t n_games,
               uint32_t n_plies, uint64_t* bitmap, uint64_t* digests, dc_replay_stats* stats);
 int dc_replay_device(dc_ctx* ctx, uint32_t rules, const dc_pos* start, const uint16_t* d_moves,

@@ -226,6 +226,23 @@ void or_fast_replay(const uint16_t* moves, uint32_t n_games, uint32_t n_plies, i
   }
 }
 
+// or_fast_replay from a given start position (cells == nullptr: the start position).
+void or_fast_replay_from(const int8_t* cells, uint8_t stm, uint8_t castle, int8_t ep, const uint16_t* moves,
+                         uint32_t n_games, uint32_t n_plies, int rules, unsigned threads, uint64_t* bitmap,
+                         uint64_t* digests, uint64_t* stats) {
+  const fastcpu::Pos start = fast_pos(cells, stm, castle, ep);
+  fastcpu::ReplayStats st;
+  fastcpu::replay(&start, moves, n_games, n_plies, static_cast<fastcpu::Rules>(rules), bitmap, digests, &st,
+                  threads);
+  if (stats) {
+    stats[0] = st.validated;
+    stats[1] = st.accepted;
+    stats[2] = st.rejected;
+    stats[3] = st.digest_sum;
+    stats[4] = st.digest_xor;
+  }
+}
+
 void or_fast_quad(const int8_t* cells, uint64_t* bb) {
   fastcpu::Pos p = fast_pos(cells, 0, 0, -1);
   fastcpu::to_quad(p, bb);

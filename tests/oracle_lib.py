@@ -56,6 +56,8 @@ def lib():
         L.or_fast_gen_games.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                         _u16p, C.c_uint]
         L.or_fast_replay.argtypes = [_u16p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint, _u64p, _u64p, _u64p]
+        L.or_fast_replay_from.argtypes = [_i8p, C.c_uint8, C.c_uint8, C.c_int8, _u16p, C.c_uint32, C.c_uint32,
+                                          C.c_int, C.c_uint, _u64p, _u64p, _u64p]
         L.or_fast_quad.argtypes = [_i8p, _u64p]
         L.or_fast_digest.restype = C.c_uint64
         L.or_fast_digest.argtypes = [_i8p, C.c_uint8]
@@ -182,7 +184,8 @@ def fast_gen_games(seed, first_game, n_games, n_plies, noise_per_256=32, rules=R
     return out
 
 
-def fast_replay(moves, rules=REF, threads=None):
+def fast_replay(moves, rules=REF, threads=None, start=None):
+    """start: a Pos to replay every game from (None = the start position)."""
     threads = threads or min(8, os.cpu_count() or 1)
     moves = np.ascontiguousarray(moves, dtype=np.uint16)
     n_plies, n_games = moves.shape
@@ -190,8 +193,12 @@ def fast_replay(moves, rules=REF, threads=None):
     bitmap = np.zeros((n_plies, words), np.uint64)
     dig = np.zeros(n_games, np.uint64)
     st = np.zeros(5, np.uint64)
-    lib().or_fast_replay(_p(moves, _u16p), n_games, n_plies, rules, threads, _p(bitmap, _u64p), _p(dig, _u64p),
-                         _p(st, _u64p))
+    if start is None:
+        lib().or_fast_replay(_p(moves, _u16p), n_games, n_plies, rules, threads, _p(bitmap, _u64p), _p(dig, _u64p),
+                             _p(st, _u64p))
+    else:
+        lib().or_fast_replay_from(_p(start.cells, _i8p), start.stm, start.castle, start.ep, _p(moves, _u16p),
+                                  n_games, n_plies, rules, threads, _p(bitmap, _u64p), _p(dig, _u64p), _p(st, _u64p))
     return bitmap, dig, st
 
 
