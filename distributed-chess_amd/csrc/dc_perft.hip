@@ -1669,7 +1669,10 @@ struct C2cShared {
   u32 queue[4][kC2cQueue];
   u32 queue_d[4][kC2cQueue];
   u32 queue_q[4][kC2cQueue];
-  u64 hist[256];
+  union {
+    u64 hist[256];
+    u32 sums[256];  // c2c_group<.., PARSUM>: leaves under each of the group's parents
+  };
   u64 wsum[6];  // scans; the pooled final drains' per-wave leftovers (12 u32)
   u32 next;
   // (the tag is written by put_tag before the parent split: fewer live VGPRs there)
@@ -1723,9 +1726,20 @@ __device__ __forceinline__ u32 c2c_diag(const C2cShared<CAP>& sh, u32 e) {
 // Called by k_count2c (parents read from a level in HBM) and k_perft_dfs
 // (parents produced by each lane's DFS stack).  Block-uniform call; ends with
 // a block barrier (par/att/ptag/slot are reused by the next group).
-template <int STM, u32 CAP, int PHASE = 0, bool BULK = true>
+// PARSUM (k_count3c<.., DEDUP>): the leaves are summed per parent instead, in
+// sh.sums (which overlays sh.hist), and the caller takes sums[its own thread]
+// after the closing barrier; `tag`, hist and divide are not used.  A child's
+// count goes to sums[pl] with one 32-bit LDS add (pl, the parent's thread, is
+// in every slot and queue entry; a parent has at most 218 x 218 leaves), where
+// the histogram needs the record's tag, a compare with tag0 and, for every tag
+// but the group's first, a 64-bit add that a wave's lanes send to one or two
+// addresses when the tags are grandparents (about 11 to a group).  The parent's
+// own lane stores its simple children's leaves before the first barrier, which
+// also re-initialises its entry for this group.
+template <int STM, u32 CAP, int PHASE = 0, bool BULK = true, bool PARSUM = false>
 __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const Board& p, u32 tag,
                                           u64* __restrict__ divide, u32 wave) {
+  static_assert(!PARSUM || (PHASE == 0 && BULK), "per-parent sums: the bulk split, counting");
   // wave: this wave's index in the block (an SGPR, readfirstlane at kernel
   // entry); the thread index is rebuilt where it is used (otid)
   const u32 w = wave, lane = lane_id();
@@ -1744,7 +1758,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   u32 nsim = 0;
   constexpr bool REUSE = GQ;
   u64 tgt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (REUSE) slider target sets, compile-time indexed
-  sh.put_tag(otid(w), tag);  // (the previous group ended with a barrier)
+  if constexpr (!PARSUM) sh.put_tag(otid(w), tag);  // (the previous group ended with a barrier)
   if (valid) {
     if constexpr (BULK) {
       ParentSplit ps;
@@ -1765,21 +1779,31 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
       base = ref_count_nonpawn<1 - STM>(p, att);
     }
   }
+  // (PARSUM: this thread's entry was last read by this thread, after the
+  // previous group; the other threads' adds into it come after the scan's barrier)
+  if constexpr (PARSUM) sh.sums[otid(w)] = (u32)simple_leaves;
   u32 total;  // (at most 256 parents x 218 moves)
   const u32 excl = block_excl_scan32<4>(cnt, reinterpret_cast<u32*>(sh.wsum), &total, w);
   sh.put(otid(w), p, att, base, orth, diag);
   __syncthreads();
-  const u32 tag0 = sh.tag(0);
-  u64 acc = 0;  // grandchildren under parents whose tag == tag0
-  // k leaves under the root move `ptag` (read with the record, so no LDS
-  // round trip of its own)
+  [[maybe_unused]] u32 tag0 = 0;
+  if constexpr (!PARSUM) tag0 = sh.tag(0);
+  [[maybe_unused]] u64 acc = 0;  // grandchildren under parents whose tag == tag0
+  // the key the leaves under parent `pl` are added under: its root move (read
+  // with the record, so no LDS round trip of its own), or (PARSUM) pl itself
+  auto key = [&](u32 pl) { return PARSUM ? pl : sh.tag(pl); };
+  // k leaves under the key `ptag`
   auto add_tag = [&](u32 ptag, u32 k, bool live) {
     if constexpr (PHASE == 7) return;
     if (!live) return;
-    if (ptag == tag0) acc += k;
-    else if (k) atomicAdd((unsigned long long*)&sh.hist[ptag], (unsigned long long)k);
+    if constexpr (PARSUM) {
+      atomicAdd(&sh.sums[ptag], k);
+    } else {
+      if (ptag == tag0) acc += k;
+      else if (k) atomicAdd((unsigned long long*)&sh.hist[ptag], (unsigned long long)k);
+    }
   };
-  auto add = [&](u32 pl, u32 k, bool live) { add_tag(sh.tag(pl), k, live); };
+  auto add = [&](u32 pl, u32 k, bool live) { add_tag(key(pl), k, live); };
   u32 qn = 0, qnd = 0;  // queue lengths: wave-uniform (kept scalar via readfirstlane)
   // One candidate child: its parent's LDS record is loaded first (so two
   // candidates' loads can be in flight together), then the short path if the
@@ -1857,7 +1881,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   auto drain64 = [&]() {  // qn >= 64: recount 64 queued children in full
     wave_lds_sync();
     const u32 e2 = q[lane];
-    const u32 tg = sh.tag(e2 >> 15);  // issued with the record reads
+    const u32 tg = key(e2 >> 15);  // issued with the record reads
     add_tag(tg, PHASE == 5 || PHASE == 6 ? e2 & 1 : c2c_full<STM>(sh, e2), true);
     wave_lds_sync();
     if (lane + 64 < qn) q[lane] = q[lane + 64];
@@ -1866,7 +1890,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   auto drain64d = [&]() {  // qnd >= 64: count 64 queued children group-wise
     wave_lds_sync();
     const u32 e2 = qd[lane];
-    const u32 tg = sh.tag(e2 >> 15);
+    const u32 tg = key(e2 >> 15);
     add_tag(tg, PHASE == 5 || PHASE == 6 ? e2 & 1 : c2c_diag<STM>(sh, e2), true);
     wave_lds_sync();
     if (lane + 64 < qnd) qd[lane] = qd[lane + 64];
@@ -1881,7 +1905,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   auto drain64q = [&]() {  // qnq >= 64: 64 queued quiet children
     wave_lds_sync();
     const u32 e2 = qq[lane];
-    const u32 tg = sh.tag(e2 >> 15);
+    const u32 tg = key(e2 >> 15);
     add_tag(tg, quiet_count(e2), true);
     wave_lds_sync();
     if (lane + 64 < qnq) qq[lane] = qq[lane + 64];
@@ -1892,7 +1916,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
     if constexpr (GQ) if (qnd >= 64) drain64d();
     if constexpr (QQ) if (qnq >= 64) drain64q();
   };
-  if constexpr (BULK && PHASE != 7) add(otid(w), (u32)simple_leaves, valid);
+  if constexpr (BULK && PHASE != 7 && !PARSUM) add(otid(w), (u32)simple_leaves, valid);
   if constexpr (PHASE == 7) {  // [2] simple children, [3] parents
     const u64 ns = wave_sum64(nsim), np = __popcll(ballot(valid));
     if (lane == 0) {
@@ -2010,8 +2034,8 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
       add(e2 >> 15, r, live);
     }
   }
-  tag_hist_add(sh.hist, tag0, acc, true);
-  __syncthreads();  // par/att/ptag/slot reused by the next group
+  if constexpr (!PARSUM) tag_hist_add(sh.hist, tag0, acc, true);
+  __syncthreads();  // par/att/ptag/slot reused by the next group (PARSUM: the sums are complete)
 }
 
 #ifdef DC_AB_KNOBS
@@ -2105,11 +2129,12 @@ constexpr u32 kMoveWordNodes = 1u << 20;  // grandparent index field of a move w
 // the host reruns in exact mode, which takes the k_level_write path.
 // DEDUP (after a deduplicating k_front): `divide` is gp_total, one u64 per
 // grandparent, and `tags` is not read.  The words are sorted by grandparent and
-// every grandparent written has a word, so a group's 256 words span fewer than
-// 256 consecutive grandparents: c2c_group gets the grandparent's index
-// relative to the group's first as its tag, and the block's histogram is
-// added into gp_total and cleared after every group (a grandparent's words
-// can straddle two groups).  k_front_fold turns gp_total into the divide.
+// a thread's tag is its word's grandparent index, kept in a register.
+// c2c_group sums the leaves per parent (PARSUM: no histogram, the tag is not
+// used there), and after every group each wave adds its runs of equal tags
+// into gp_total, one atomic per run (a grandparent's words can straddle two
+// waves or two groups: it then gets an add from each).  k_front_fold turns
+// gp_total into the divide.
 template <int STM_G, u32 CAP, int MINW = 4, class W = u32, bool DEDUP = false>
 __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__ nodes, const uint16_t* __restrict__ tags,
                                                  const Range* __restrict__ rng, const Range* __restrict__ rng_ch,
@@ -2123,7 +2148,7 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
       fst->incl[k] = 0;
     }
   }
-  tag_hist_init(sh.hist);
+  if constexpr (!DEDUP) tag_hist_init(sh.hist);
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool t0 = wave == 0 && lane_id() == 0;
   const u64 lo = rng->lo;
@@ -2143,7 +2168,11 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
   for (;;) {
     // (fetching the next group's index one group ahead, to take its round
     // trip off the load chain, made the kernel 0.495 -> 0.519 ms at perft(7):
-    // a block then holds a group it cannot start, which lengthens the tail)
+    // a block then holds a group it cannot start, which lengthens the tail.
+    // Bounded to all but the last two rounds of the grid, with the next
+    // group's word loaded ahead too, the DEDUP kernel's perft(7) step went
+    // 0.169 -> 0.176 ms on two contexts and 0.202 -> 0.232 ms on one:
+    // DESIGN.md section 3.9, profiles/parent_sums/step2/)
     const u64 s = (u64)grp * kGroup;
     if (s >= total) break;  // block-uniform
     const u32 ot = otid(wave);
@@ -2151,28 +2180,33 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
     const bool valid = ot < kGroup && i < total;
     Board ch{0, 0, 0, 0};
     u32 tag = 0;
-    [[maybe_unused]] u32 g_first = 0;  // DEDUP: the group's first grandparent (block-uniform)
-    if constexpr (DEDUP) g_first = (u32)(mw[s] >> 12);
     if (valid) {
       const W e = mw[i];
       const u64 g = lo + (u64)(e >> 12);
       ch = load_board(nodes, g);
-      if constexpr (DEDUP) tag = (u32)(e >> 12) - g_first;
+      if constexpr (DEDUP) tag = (u32)(e >> 12);
       else tag = tags[g];
       const u32 mv = (u32)e;
       ref_make(ch, (int)(mv & 63), (int)((mv >> 6) & 63));
     }
-    c2c_group<1 - STM_G, CAP>(sh, valid, ch, tag, divide, wave);
+    c2c_group<1 - STM_G, CAP, 0, true, DEDUP>(sh, valid, ch, tag, divide, wave);
     // (c2c_group ended with a barrier: every thread is past its read of grp's state)
     if constexpr (DEDUP) {
-      // (the next group's first add into hist comes after c2c_group's first barrier)
-      if (ot < 256) {
-        const u64 v = sh.hist[ot];
-        if (v) {
-          atomicAdd((unsigned long long*)(divide + lo + g_first + ot), (unsigned long long)v);
-          sh.hist[ot] = 0;
-        }
-      }
+      // This thread's parent's leaves (0 for an empty slot; the thread itself
+      // overwrites the entry in the next group, before c2c_group's first
+      // barrier).  The words are sorted by grandparent, so a grandparent's parents
+      // are a run of lanes: the wave's inclusive scan, less its value before
+      // the run's first lane, is the run's sum at the run's last lane, which
+      // adds it into gp_total.  (A sum is below 64 x 218 x 218.)
+      const u32 lane = lane_id();
+      const u32 inc = wave_incl_scan(sh.sums[ot]);
+      const u32 left = (u32)__shfl_up((int)tag, 1);
+      const u64 heads = ballot(lane == 0 || tag != left);
+      const u32 head = (u32)msb(heads & (~0ull >> (63 - lane)));  // this lane's run starts here (bit 0 is set)
+      const u32 before = (u32)__shfl((int)inc, (int)((head + 63) & 63));
+      const u32 run = inc - (head ? before : 0u);
+      const bool last = lane == 63 || (((heads >> 1) >> lane) & 1);
+      if (last && run) atomicAdd((unsigned long long*)(divide + lo + tag), (unsigned long long)run);
     }
     if (t0) sh.next = gridDim.x + atomicAdd(next_group, 1u);
     __syncthreads();
