@@ -22,11 +22,6 @@ struct LegalIo {
 extern "C" {
 
 // ============================================================= legal moves
-static bool legal_plain() {
-  const char* e = dc::ab_env("DC_LEGAL_EMIT");  // A/B build only
-  return e && std::strcmp(e, "plain") == 0;
-}
-
 static int legal_io_ensure(dc_ctx* c) {
   if (c->legal_io) return DC_SUCCESS;
   HIP_TRY(c->legal_io.alloc(hipHostMallocCoherent));
@@ -45,7 +40,7 @@ static int legal_small(dc_ctx* c, uint32_t rules, const DevPos* pos, uint32_t n,
   uint32_t* done = flag ? &h->done : nullptr;
   HIP_TRY(c->timed("legal_small", n, [&] {
     return dc::launch_legal_small(c->stream, rules, pos, n, offsets, status, moves, cap,
-                                  reinterpret_cast<u64*>(&h->total), done, seq, legal_plain());
+                                  reinterpret_cast<u64*>(&h->total), done, seq);
   }));
   const int e = flag ? wait_host_flag(c, done, seq) : sync_ctx(c);
   if (e != DC_SUCCESS) return e;
@@ -80,7 +75,7 @@ static int legal_finish(dc_ctx* c, uint32_t rules, const DevPos* d_pos, uint32_t
   if (d_moves) {
     HIP_TRY(c->timed("legal_emit", total, [&] {
       return dc::launch_legal_emit(c->stream, rules, d_pos, n, d_offsets, c->legal_bsum.p, c->legal_bbase.p, d_moves,
-                                   total, legal_plain());
+                                   total);
     }));
   } else {
     HIP_TRY(c->timed("legal_fixup", n, [&] {

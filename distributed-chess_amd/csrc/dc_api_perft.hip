@@ -13,7 +13,7 @@
 // end.  Writes past a capacity are dropped and flagged; the run is then
 // repeated in exact mode, which reads every level size back before sizing the
 // next (one sync per level).  Level order is deterministic, so ranks that
-// rebuild the top levels agree on the frontier and take contiguous shards.
+// rebuild the top levels agree on the frontier and on each one's shard of it.
 namespace {
 
 constexpr u64 kBranchBound = 64;                    // speculative children per node
@@ -67,14 +67,9 @@ int read_range(dc_ctx* c, int level, u64* n) {
   return DC_SUCCESS;
 }
 
-// The experiment knobs of this driver (A/B build only: the product reads none,
+// The experiment knob of this driver (A/B build only: the product reads none,
 // see ab_env), read once per process.
 struct Knobs {
-  bool fused3 = dc::ab_flag("DC_FUSED3", true);         // 0: the last level is written and counted by k_count2c
-  bool front = dc::ab_flag("DC_FRONT", true);           // 0: REF perft(6) / perft(7) take the round-5 chain
-  bool graphs = dc::ab_flag("DC_GRAPH", true);          // 0: no perft graphs
-  bool fide_top3 = dc::ab_flag("DC_FIDE_TOP3", false);  // 1: the round-4 plan, three plies in the one workgroup
-  bool shard_contig = dc::ab_is("DC_SHARD", "contig");  // a rank's shard: a contiguous part, not every n-th node
   // Which k_front shapes deduplicate their grandparents (DESIGN.md section 3.9:
   // decided by measurement).  A mask: 1 perft(7) unsharded, 2 perft(7) shards,
   // 4 perft(6) unsharded, 8 perft(6) shards.
@@ -162,7 +157,7 @@ static u32 top_plies(bool fide, bool exact, u32 deepest, bool sharded, u32 S) {
   // nodes) made inside the one workgroup was ~0.3 ms per position (rocprofv3,
   // round 4); stopping the top kernel one ply short leaves it to the level
   // kernels on every CU
-  if (fide && !exact && T == deepest && deepest == 3 && !knobs().fide_top3) T = deepest - 1;
+  if (fide && !exact && T == deepest && deepest == 3) T = deepest - 1;
   return sharded ? std::min(T, S) : T;
 }
 
@@ -171,13 +166,7 @@ static PerftShape perft_shape(const PerftReq& q, bool exact) {
   const uint32_t depth = q.depth, split_depth = q.split_depth;
   PerftShape s{};
   s.F = depth >= 3 ? depth - 2 : 1;
-  // (the sliced stage indexes its grandparent level from 0: a contiguous shard
-  // cut at that very level (DC_SHARD=contig, A/B build) starts elsewhere, so
-  // that combination takes K4 instead)
-  const bool contig_at_sliced =
-      knobs().shard_contig && sharded && depth == kDfsFrontier + 4 && shard_level(split_depth, s.F) == depth - 3;
-  s.wide = !fide && (depth == kDfsFrontier + 3 || depth == kDfsFrontier + 4) && !perft_k4_forced() &&
-           !contig_at_sliced;
+  s.wide = !fide && (depth == kDfsFrontier + 3 || depth == kDfsFrontier + 4) && !perft_k4_forced();
   s.sliced = s.wide && depth == kDfsFrontier + 4;
   // REF beyond ply kDfsFrontier: K4 walks the last Ldfs plies above the final
   // stage per lane (k_perft_dfs) instead of materialising those levels
@@ -193,14 +182,14 @@ static PerftShape perft_shape(const PerftReq& q, bool exact) {
   // never written; its parents' level is counted and scanned, then expanded
   // group by group inside the final stage.  Needs a level to expand (L < F)
   // that is not the shard level.
-  s.fused3 = !fide && s.Ldfs == 0 && s.final_plies == 2 && s.T < s.F && !(sharded && s.S == s.F) && knobs().fused3;
+  s.fused3 = !fide && s.Ldfs == 0 && s.final_plies == 2 && s.T < s.F && !(sharded && s.S == s.F);
   // The target ply of k_expand_top is made on many CUs by k_make_count (it
   // replaces that level's k_level_count) when that level is counted next.
   // A rank's strided shard of that ply (round 5): the words stay whole and
   // k_make_count makes only this rank's (word shard + i x n_shards), instead
   // of the one workgroup making the whole ply as boards and k_gather_shard
   // copying the shard out of it.
-  s.shard_words = !exact && sharded && s.S == s.T && s.T >= 2 && s.T < s.F && !knobs().shard_contig;
+  s.shard_words = !exact && sharded && s.S == s.T && s.T >= 2 && s.T < s.F;
   s.top_words = !exact && s.T >= 2 && s.T < s.F && (!(sharded && s.S == s.T) || s.shard_words);
   return s;
 }
@@ -208,9 +197,8 @@ static PerftShape perft_shape(const PerftReq& q, bool exact) {
 // REF perft(6) / perft(7) of one root, unsharded or a strided shard of ply 3:
 // the one-launch front end (k_front) + k_count3c.
 static bool front_eligible(const PerftReq& q) {
-  if (q.rules != DC_RULES_REF || q.n_pos != 1 || (q.depth != 6 && q.depth != 7) || !knobs().front || !knobs().fused3)
-    return false;
-  return !q.sharded() || (perft_shape(q, false).S == 3 && !knobs().shard_contig);
+  if (q.rules != DC_RULES_REF || q.n_pos != 1 || (q.depth != 6 && q.depth != 7)) return false;
+  return !q.sharded() || perft_shape(q, false).S == 3;
 }
 
 // The buffers every perft sequence needs, allocated before anything is enqueued.
@@ -326,7 +314,6 @@ struct LevelChain {
   bool* host_sync;   // which sets this: the sequence then depends on data (never captured)
   bool sharded;      // a shard of level S is taken
   u32 S, T;
-  bool contiguous;   // the shard: a contiguous part of the level (DC_SHARD=contig) instead of every n-th node
   bool top_words;    // level T is still k_expand_top's move words: the first count_and_scan makes it
   bool shard_words;  // ... and makes only this rank's strided shard of it (S == T)
   dc::TopScratch ts{};
@@ -385,10 +372,6 @@ struct LevelChain {
     if (!sharded) return DC_SUCCESS;
     if (shard_words) {  // the words stay whole: only the level's Range becomes the shard's
       HIP_TRY(dc::launch_shard_range(c->stream, c->rng.p + L, q.shard, q.n_shards));
-      return DC_SUCCESS;
-    }
-    if (contiguous) {
-      HIP_TRY(dc::launch_slice(c->stream, c->rng.p + L, q.shard, q.n_shards));
       return DC_SUCCESS;
     }
     int e = ensure_level(c, buf ^ 1, nb, fide());
@@ -471,7 +454,7 @@ int perft_enqueue(dc_ctx* c, const PerftReq& q, bool exact, bool front, bool sta
   if (sh.Ldfs > 3) return DC_EUNSUPPORTED;
   u32 F = sh.F, Ldfs = sh.Ldfs;  // (exact mode may move both to K4 below)
   const bool wide = sh.wide, sliced = sh.sliced, fused3 = sh.fused3;
-  LevelChain ch{c, q, exact, host_sync, q.sharded(), sh.S, sh.T, knobs().shard_contig, sh.top_words, sh.shard_words};
+  LevelChain ch{c, q, exact, host_sync, q.sharded(), sh.S, sh.T, sh.top_words, sh.shard_words};
   int e = ch.begin(sh.cap_T, stage_root, q.fide());
   if (e != DC_SUCCESS) return e;
   // Capacity of level L + 1 (and the node guard of level L) in speculative
@@ -627,7 +610,7 @@ static bool end_capture(dc_ctx* c, uint64_t key_epoch, bool ok_so_far, hipGraphE
 // which removes the per-kernel launch gaps.  The root position
 // is read from the pinned staging block when the graph runs.
 int perft_run(dc_ctx* c, const PerftReq& q, bool exact, bool front, dc::PerftResult* out) {
-  const bool graphable = !exact && !c->profiling && knobs().graphs;
+  const bool graphable = !exact && !c->profiling;
   front = front && !exact;
   const dc_ctx::PerftKey key = perft_key(q, front);
   if (graphable && c->pgraph && c->pkey == key) {
@@ -737,7 +720,7 @@ int stats_enqueue(dc_ctx* c, const PerftReq& q, bool exact) {
   bool host_sync = false;  // (nothing here is captured)
   // boards at every level, every n-th node as the shard; at depth 1 nothing is
   // cut (shard 0 holds the root's moves, as dc_perft_shard's depth 1)
-  LevelChain ch{c, q, exact, &host_sync, q.sharded() && F > 0, S, T, false, false, false};
+  LevelChain ch{c, q, exact, &host_sync, q.sharded() && F > 0, S, T, false, false};
   // (the meta goes up under REF too: the device root then always equals the
   // staged one, which is what root_staged lets a later captured run assume)
   int e = ch.begin(cap_T, true, true);
@@ -909,7 +892,7 @@ static int repeat_runs(dc_ctx* c, const PerftReq& q, uint32_t n_runs, uint64_t* 
   HIP_TRY(c->rcur.ensure(1));  // before the key: an allocation moves the epoch
   // (a graph captured after a declined front holds the legacy chain: front false)
   dc_ctx::PerftKey key = perft_key(q, front_eligible(q));
-  const bool graphable = !c->profiling && knobs().graphs;
+  const bool graphable = !c->profiling;
   // capture `runs` runs of the sequence back to back (the result copy is part
   // of the graph: its destination is the cursor)
   auto capture = [&](u32 runs, hipGraphExec_t* out) {

@@ -194,21 +194,6 @@ __device__ __forceinline__ u64 splitmix_next(u64& s) {
   return z ^ (z >> 31);
 }
 
-// k-th (0-based) set bit of x; x must have more than k bits set.
-__device__ __forceinline__ int select_bit(u64 x, u32 k) {
-  const u32 lo = (u32)x;
-  const u32 nlo = (u32)__popc(lo);
-  int base = 0;
-  u32 w = lo;
-  if (k >= nlo) {
-    k -= nlo;
-    w = (u32)(x >> 32);
-    base = 32;
-  }
-  for (u32 i = 0; i < k; ++i) w &= w - 1;
-  return base + __ffs(w) - 1;
-}
-
 // k-th (0-based) set bit of x without a data-dependent loop: five halving
 // steps on popcounts, then the last bit (x must have more than k bits set).
 __device__ __forceinline__ u32 select_bit_bf(u64 x, u32 k) {

@@ -25,7 +25,7 @@ static inline bool ab_flag(const char* name, bool def) {
   const char* e = ab_env(name);
   return (e && e[0] == (def ? '0' : '1')) ? !def : def;
 }
-// A knob that selects a named variant (DC_SHARD=contig, DC_FINAL=2b).
+// A knob that selects a named variant (NAME=value; no knob of this form is open now).
 static inline bool ab_is(const char* name, const char* value) {
   const char* e = ab_env(name);
   return e && strcmp(e, value) == 0;

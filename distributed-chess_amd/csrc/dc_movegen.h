@@ -16,7 +16,7 @@ enum : u32 { ST_CHECK = 1, ST_NO_MOVES = 2, ST_DEAD = 4 };
 // total fits `cap`.  done / seq: the completion flag of dc_moves.hip's
 // publish_done (pinned I/O), or nullptr.
 hipError_t launch_legal_small(hipStream_t st, u32 rules, const DevPos* pos, u32 n, u32* offsets, uint8_t* status,
-                              uint16_t* moves, u32 cap, u64* total, u32* done, u32 seq, bool plain);
+                              uint16_t* moves, u32 cap, u64* total, u32* done, u32 seq);
 // Any n: offsets[i] = exclusive prefix of the counts inside i's block,
 // block_sum[b] = the block's count.
 hipError_t launch_legal_count(hipStream_t st, u32 rules, const DevPos* pos, u32 n, u32* offsets, uint8_t* status,
@@ -31,6 +31,6 @@ hipError_t launch_legal_fixup(hipStream_t st, u32* offsets, u32 n, const u32* bl
 // Writes every position's moves at its final offset and the final offsets;
 // nothing at or past moves[limit].
 hipError_t launch_legal_emit(hipStream_t st, u32 rules, const DevPos* pos, u32 n, u32* offsets, const u32* block_sum,
-                             const u32* block_base, uint16_t* moves, u32 limit, bool plain);
+                             const u32* block_base, uint16_t* moves, u32 limit);
 
 }  // namespace dc

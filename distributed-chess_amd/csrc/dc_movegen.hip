@@ -2,22 +2,16 @@
 //
 //   k_legal_count<G>   counts and status, block-local exclusive prefix -> offsets, block sums
 //   k_legal_scan       one workgroup: 64-bit exclusive prefix of the block sums, the total
-//   k_legal_emit<G,S>  every lane re-derives its moves in canonical order and
+//   k_legal_emit<G>    every lane re-derives its moves in canonical order and
 //                      writes them at its final offset (and the final offsets)
 //   k_legal_fixup      the sizing call's offsets (no moves wanted)
-//   k_legal_small<G,S> n <= 256: all of the above in one block, one launch
+//   k_legal_small<G>   n <= 256: all of the above in one block, one launch
 //
 // The output is a dense CSR, so the lanes of a wave own adjacent ranges of the
-// move array: a wave's moves are one contiguous run of u16.  The staged emit
-// (S = true) collects that run in LDS, kStageChunk moves at a time, at the
-// lanes' wave-prefix offsets, and streams it out as aligned dwords (an odd
-// first or last u16 goes out on its own); the plain emit (S = false) stores
-// each move straight from its lane.  The plain emit ships; the A/B build also
-// holds the staged one (DC_LEGAL_EMIT=plain|staged).  Why plain: at 1M
-// positions it took 0.51 ms against the staged one's 0.74 ms (DESIGN.md
-// section 3.10) -- the kernel is bound by re-deriving the moves
-// piece by piece, not by its stores, and staging adds LDS traffic, two wave
-// syncs per chunk and a second enumeration for lanes that straddle chunks.
+// move array; each move is stored straight from its lane.  (An emit that staged
+// a wave's run in LDS and streamed it out as aligned dwords took 0.74 ms at 1M
+// positions against 0.51 ms and was removed, DESIGN.md section 3.10: the kernel
+// is bound by re-deriving the moves piece by piece, not by its stores.)
 //
 // No kernel waits for another block: count, scan and emit are three launches.
 #include <hip/hip_runtime.h>
@@ -29,11 +23,7 @@ namespace dc {
 
 namespace {
 
-constexpr u32 kStageChunk = 2048;            // moves staged per wave and round (even: a run keeps its parity)
-constexpr u32 kStageWave = kStageChunk + 8;  // + the parity slot, padded to 16 bytes
-constexpr u32 kPosWords = kLegalBlock * 5;   // a block's positions as u64
-constexpr u32 kSmemWords = (4 * kStageWave * 2 + 7) / 8 > kPosWords ? (4 * kStageWave * 2 + 7) / 8 : kPosWords;
-static_assert(kStageChunk % 2 == 0 && (kStageWave * 2) % 16 == 0, "stage layout");
+constexpr u32 kPosWords = kLegalBlock * 5;  // a block's positions as u64
 
 struct LanePos {
   Board b;
@@ -67,7 +57,7 @@ struct RefGen {
   static constexpr bool kFide = false;
   static __device__ __forceinline__ u32 count(const LanePos& p) { return ref_count_rt(p.b, p.stm); }
   static __device__ __forceinline__ u32 status(const LanePos&) { return 0; }  // kings are capturable: no check, no dead
-  // (from, to) ascending: ref_kth_move's order
+  // (from, to) ascending: the REF game generator's order
   template <class Sink>
   static __device__ __forceinline__ void list(const LanePos& p, Sink&& sink) {
     const u64 occ = occupied(p.b);
@@ -168,52 +158,16 @@ __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* wsum /*LDS[4]*/, u32*
 // ascending.  The enumeration is cut at cnt and padded with DC_MOVE_NONE should
 // it come short (count and enumeration agree on every position with at most
 // one king per side), so a lane never leaves its own range.
-template <class G, bool STAGED>
-__device__ __forceinline__ void emit_wave(const LanePos& p, u32 start, u32 cnt, uint16_t* __restrict__ moves, u32 limit,
-                                          uint16_t* stage /*LDS[kStageWave], this wave's*/) {
-  if constexpr (!STAGED) {
-    (void)stage;
-    if (cnt == 0) return;
-    u32 k = 0;
-    auto sink = [&](u32 mv) {
-      if (k < cnt && start + k < limit) moves[start + k] = (uint16_t)mv;
-      ++k;
-    };
-    G::list(p, sink);
-    while (k < cnt) sink(0xFFFFu);
-  } else {
-    const u32 lane = lane_id();
-    const u32 w0 = lane_bcast(start, 0);
-    const u32 wtot = lane_bcast(start + cnt, 63) - w0;
-    if (wtot == 0) return;
-    // 1 when the run starts on an odd u16 of its dword: the staged copy is
-    // shifted by one slot, so staged dwords are memory dwords
-    const u32 par = (u32)((reinterpret_cast<uintptr_t>(moves + w0) >> 1) & 1);
-    const u32 rel = start - w0, end = rel + cnt;
-    for (u32 c0 = 0; c0 < wtot; c0 += kStageChunk) {
-      const u32 m = min(kStageChunk, wtot - c0);
-      if (cnt != 0 && rel < c0 + m && end > c0) {  // the lane's range meets this chunk
-        u32 k = rel;
-        auto sink = [&](u32 mv) {
-          const u32 x = k - c0;  // before the chunk: wraps past m
-          if (x < m && k < end) stage[x + par] = (uint16_t)mv;
-          ++k;
-        };
-        G::list(p, sink);
-        while (k < end) sink(0xFFFFu);
-      }
-      wave_lds_sync();
-      const u32 g0 = w0 + c0;
-      if (par && lane == 0 && g0 < limit) moves[g0] = stage[1];
-      const u32 body = (m - par) >> 1;  // whole dwords after the odd head
-      u32* __restrict__ gd = reinterpret_cast<u32*>(moves + g0 + par);
-      const u32* sd = reinterpret_cast<const u32*>(stage) + par;
-      for (u32 d = lane; d < body; d += 64)
-        if (g0 + par + 2 * d + 1 < limit) gd[d] = sd[d];
-      if (((m - par) & 1) && lane == 0 && g0 + m - 1 < limit) moves[g0 + m - 1] = stage[m - 1 + par];
-      wave_lds_sync();
-    }
-  }
+template <class G>
+__device__ __forceinline__ void emit_wave(const LanePos& p, u32 start, u32 cnt, uint16_t* __restrict__ moves, u32 limit) {
+  if (cnt == 0) return;
+  u32 k = 0;
+  auto sink = [&](u32 mv) {
+    if (k < cnt && start + k < limit) moves[start + k] = (uint16_t)mv;
+    ++k;
+  };
+  G::list(p, sink);
+  while (k < cnt) sink(0xFFFFu);
 }
 
 // Completion flag of a one-block launch whose outputs are pinned host memory
@@ -228,9 +182,8 @@ __device__ __forceinline__ void legal_publish_done(u32* done, u32 seq) {
   }
 }
 
-template <bool STAGED>
 struct LegalShared {
-  alignas(16) u64 mem[STAGED ? kSmemWords : kPosWords];  // the block's positions, then the waves' stages
+  alignas(16) u64 mem[kPosWords];  // the block's positions
   u32 wsum[kLegalBlock / 64];
 };
 
@@ -238,7 +191,7 @@ struct LegalShared {
 template <class G>
 __global__ __launch_bounds__(kLegalBlock) void k_legal_count(const DevPos* __restrict__ pos, u32 n, u32* __restrict__ offsets,
                                                              uint8_t* __restrict__ status, u32* __restrict__ block_sum) {
-  __shared__ LegalShared<false> sh;
+  __shared__ LegalShared sh;
   const u32 first = blockIdx.x * kLegalBlock, i = first + threadIdx.x;
   const bool active = i < n;
   const LanePos p = load_block_pos(pos, first, n, sh.mem, G::kFide);
@@ -290,12 +243,12 @@ __global__ __launch_bounds__(kLegalBlock) void k_legal_fixup(u32* __restrict__ o
   if (i < n) offsets[i] += block_base[blockIdx.x];
 }
 
-template <class G, bool STAGED>
+template <class G>
 __global__ __launch_bounds__(kLegalBlock) void k_legal_emit(const DevPos* __restrict__ pos, u32 n, u32* offsets,
                                                             const u32* __restrict__ block_sum,
                                                             const u32* __restrict__ block_base,
                                                             uint16_t* __restrict__ moves, u32 limit) {
-  __shared__ LegalShared<STAGED> sh;
+  __shared__ LegalShared sh;
   const u32 tid = threadIdx.x, first = blockIdx.x * kLegalBlock, i = first + tid;
   const bool active = i < n;
   const LanePos p = load_block_pos(pos, first, n, sh.mem, G::kFide);
@@ -309,15 +262,14 @@ __global__ __launch_bounds__(kLegalBlock) void k_legal_emit(const DevPos* __rest
   }
   __syncthreads();
   if (active) offsets[i] = o + base;
-  emit_wave<G, STAGED>(p, o + base, nx - o, moves, limit,
-                       STAGED ? reinterpret_cast<uint16_t*>(sh.mem) + (tid >> 6) * kStageWave : nullptr);
+  emit_wave<G>(p, o + base, nx - o, moves, limit);
 }
 
-template <class G, bool STAGED>
+template <class G>
 __global__ __launch_bounds__(kLegalBlock) void k_legal_small(const DevPos* __restrict__ pos, u32 n, u32* __restrict__ offsets,
                                                              uint8_t* __restrict__ status, uint16_t* __restrict__ moves,
                                                              u32 cap, u64* total, u32* done, u32 seq) {
-  __shared__ LegalShared<STAGED> sh;
+  __shared__ LegalShared sh;
   const u32 tid = threadIdx.x;
   const bool active = tid < n;
   const LanePos p = load_block_pos(pos, 0, n, sh.mem, G::kFide);
@@ -333,39 +285,21 @@ __global__ __launch_bounds__(kLegalBlock) void k_legal_small(const DevPos* __res
     offsets[n] = all;
     __hip_atomic_store(total, (u64)all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  if (moves && all <= cap)
-    emit_wave<G, STAGED>(p, excl, cnt, moves, all, STAGED ? reinterpret_cast<uint16_t*>(sh.mem) + (tid >> 6) * kStageWave : nullptr);
+  if (moves && all <= cap) emit_wave<G>(p, excl, cnt, moves, all);
   legal_publish_done(done, seq);
-}
-
-// the A/B build holds both emit variants; the product only the plain one
-__host__ inline bool use_staged(bool plain) {
-#ifdef DC_AB_KNOBS
-  if (ab_env("DC_LEGAL_EMIT")) return !plain;
-#endif
-  (void)plain;
-  return false;
 }
 
 }  // namespace
 
 hipError_t launch_legal_small(hipStream_t st, u32 rules, const DevPos* pos, u32 n, u32* offsets, uint8_t* status,
-                              uint16_t* moves, u32 cap, u64* total, u32* done, u32 seq, bool plain) {
+                              uint16_t* moves, u32 cap, u64* total, u32* done, u32 seq) {
   if (n == 0 || n > kLegalBlock) return hipErrorInvalidValue;
-  const bool staged = use_staged(plain);
-#define DC_LEGAL_SMALL(G, S) \
-  hipLaunchKernelGGL((k_legal_small<G, S>), dim3(1), dim3(kLegalBlock), 0, st, pos, n, offsets, status, moves, cap, total, done, seq)
-#ifdef DC_AB_KNOBS
-  if (staged) {
-    if (rules == 0) DC_LEGAL_SMALL(RefGen, true);
-    else DC_LEGAL_SMALL(FideGen, true);
-  }
-#endif
-  if (!staged) {
-    if (rules == 0) DC_LEGAL_SMALL(RefGen, false);
-    else DC_LEGAL_SMALL(FideGen, false);
-  }
-#undef DC_LEGAL_SMALL
+  if (rules == 0)
+    hipLaunchKernelGGL(k_legal_small<RefGen>, dim3(1), dim3(kLegalBlock), 0, st, pos, n, offsets, status, moves, cap,
+                       total, done, seq);
+  else
+    hipLaunchKernelGGL(k_legal_small<FideGen>, dim3(1), dim3(kLegalBlock), 0, st, pos, n, offsets, status, moves, cap,
+                       total, done, seq);
   return hipGetLastError();
 }
 
@@ -393,23 +327,15 @@ hipError_t launch_legal_fixup(hipStream_t st, u32* offsets, u32 n, const u32* bl
 }
 
 hipError_t launch_legal_emit(hipStream_t st, u32 rules, const DevPos* pos, u32 n, u32* offsets, const u32* block_sum,
-                             const u32* block_base, uint16_t* moves, u32 limit, bool plain) {
+                             const u32* block_base, uint16_t* moves, u32 limit) {
   if (n == 0) return hipSuccess;
   const dim3 grid(blocks_for(n, kLegalBlock));
-  const bool staged = use_staged(plain);
-#define DC_LEGAL_EMIT(G, S) \
-  hipLaunchKernelGGL((k_legal_emit<G, S>), grid, dim3(kLegalBlock), 0, st, pos, n, offsets, block_sum, block_base, moves, limit)
-#ifdef DC_AB_KNOBS
-  if (staged) {
-    if (rules == 0) DC_LEGAL_EMIT(RefGen, true);
-    else DC_LEGAL_EMIT(FideGen, true);
-  }
-#endif
-  if (!staged) {
-    if (rules == 0) DC_LEGAL_EMIT(RefGen, false);
-    else DC_LEGAL_EMIT(FideGen, false);
-  }
-#undef DC_LEGAL_EMIT
+  if (rules == 0)
+    hipLaunchKernelGGL(k_legal_emit<RefGen>, grid, dim3(kLegalBlock), 0, st, pos, n, offsets, block_sum, block_base,
+                       moves, limit);
+  else
+    hipLaunchKernelGGL(k_legal_emit<FideGen>, grid, dim3(kLegalBlock), 0, st, pos, n, offsets, block_sum, block_base,
+                       moves, limit);
   return hipGetLastError();
 }
 

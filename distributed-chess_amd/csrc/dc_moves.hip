@@ -211,6 +211,8 @@ __global__ __launch_bounds__(256) void k_replay_ref(Board start, u32 stm0, const
 // deltas commute, so f and t in one dword need no special case) plus the
 // occupancy update.  The quad-bitboard is rebuilt once per game for the digest.
 // Per ply: ~40 VALU ops against ~175 for ref_verdict on registers.
+// The launcher takes this kernel only for a move array past 4 GiB, where
+// k_replay_ref4's one buffer descriptor ends.  No test drives it at that size.
 constexpr u32 kR3Threads = 1024;
 constexpr u32 kR3TabBytes = 4096 * 8 + 4096 * 4;  // btw (32 KB) + geo (16 KB)
 constexpr u32 kR3MbBytes = 8 * kR3Threads * 4;      // 32 KB: two blocks fill a CU's 160 KB
@@ -413,22 +415,18 @@ __global__ __launch_bounds__(kR3Threads) void k_replay_ref3(Mailbox mb0, u64 occ
 //   - inactive lanes (the last chunk only) replay game n-1 unmasked: their
 //     counters are dropped per chunk and their bitmap bits masked at the
 //     64-ply store, so no per-ply select;
-//   - both ballot halves go into the lanes' words under one M0 write;
-//   - LOOK = 1: the two table reads (btw, geo) of ply p + 1 issue before ply
-//     p's mailbox reads, so only the (conflict-free) mailbox round trip is on
-//     a ply's dependency chain; the random, bank-conflicted table gathers
-//     overlap the previous ply's logic.
+//   - both ballot halves go into the lanes' words under one M0 write.
 // INFO (dc_replay_info, the resync path): per ply and game one byte, the
 // moved piece's cell kind | 8 if the target held a piece (dc_apply_batch's
 // info, what update_history needs, chess.rs:156-167), 0xFF for a rejected ply;
 // ply-major like the moves.  Compiled out of the plain replay.
-// Round-3 experiment, dropped: a vacated square not cleared in the mailbox,
-// the occupancy bitboard masking its stale nibble when read, so that a
-// make-move is one LDS read-modify-write instead of two.  Measured slower
-// (10M x 80: 0.865 -> 0.998 ms, same box, profiles/r03/ab_replay_lazy.txt):
-// the kernel is bound by its per-ply dependency chain, not by LDS cycles,
-// and the occupancy test puts a 64-bit shift on that chain.
-template <int LOOK, int PF, bool DW, bool INFO = false>
+// Dropped experiments (DESIGN.md section 3 holds them):
+//   - a vacated square left in the mailbox, masked by the occupancy (round 3): 0.865 -> 0.998 ms;
+//   - the table reads of ply p + 1 issued before ply p's mailbox reads;
+//   - u16 move loads on even batches too;
+//   - eight plies of moves loaded ahead (round 2): 0.98 against 0.88 ms for four.
+constexpr int kR4Prefetch = 4;  // plies of moves loaded ahead
+template <bool DW, bool INFO = false>
 __global__ __launch_bounds__(kR3Threads) void k_replay_ref4(Mailbox mb0, u64 occ0, u32 stm0, const uint16_t* __restrict__ moves,
                                                            u32 n_games, u32 n_plies, u64* __restrict__ bitmap,
                                                            u64* __restrict__ digests, u64* __restrict__ partial,
@@ -463,7 +461,7 @@ __global__ __launch_bounds__(kR3Threads) void k_replay_ref4(Mailbox mb0, u64 occ
     // holding its move and its neighbour's and rotates its own into the low
     // half where it is used.  A u16 load is zero-extended by the compiler
     // right after the load, i.e. at the loop's back edge, where that forces
-    // s_waitcnt vmcnt(0) on all PF prefetched moves, the youngest issued one
+    // s_waitcnt vmcnt(0) on all kR4Prefetch prefetched moves, the youngest issued one
     // ply earlier.  Every use of m reads only its low 16 bits (12-bit
     // indices, 16-bit compares), so the neighbour's half is harmless.
     const u32 rot = DW ? (goff & 2u) << 3 : 0u;
@@ -478,9 +476,9 @@ __global__ __launch_bounds__(kR3Threads) void k_replay_ref4(Mailbox mb0, u64 occ
     u64 occ = occ0;
     u32 stm = stm0;
     u32 nvalw = 0, nacc = 0;
-    u32 buf[PF];
+    u32 buf[kR4Prefetch];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) buf[k] = load_move((u32)k);
+    for (int k = 0; k < kR4Prefetch; ++k) buf[k] = load_move((u32)k);
     u32 bw_lo = 0, bw_hi = 0;  // lane j holds the ballot word of ply 64q + j
     struct Tab {
       u64 bt;
@@ -490,18 +488,13 @@ __global__ __launch_bounds__(kR3Threads) void k_replay_ref4(Mailbox mb0, u64 occ
       return Tab{*reinterpret_cast<const u64*>(r4_smem + ((m << 3) & 0x7FF8u)),
                  *reinterpret_cast<const u32*>(r4_smem + 4096 * 8 + ((m << 2) & 0x3FFCu))};
     };
-    // LOOK: `nx` holds ply p's tables on entry and ply p + 1's (move mnext) on
-    // exit; their reads issue after ply p's mailbox reads, which LDS returns
-    // first (in order), so the wait for the mailbox never waits on them
-    Tab nx{0, 0};
-    auto ply_step = [&](u32 m, u32 slot, u32 mnext, u32 p) {
+    auto ply_step = [&](u32 m, u32 slot, u32 p) {
       const u32 m2 = m << 2, m3 = m << 3;
       const u32 af = __builtin_amdgcn_bitop3_b32(m << 9, tid4, 0x7000u, 0xE4);
       const u32 at = __builtin_amdgcn_bitop3_b32(m3, tid4, 0x7000u, 0xE4);
-      const Tab t0 = LOOK ? nx : tab(m);
+      const Tab t0 = tab(m);
       const u32 wf = *reinterpret_cast<const u32*>(r4_smem + kR3TabBytes + af);
       const u32 wt = *reinterpret_cast<const u32*>(r4_smem + kR3TabBytes + at);
-      if (LOOK) nx = tab(mnext);
       const u64 bt = t0.bt;
       const u32 gw = t0.gw;
       const u32 st = (m >> 4) & 28;
@@ -551,20 +544,19 @@ __global__ __launch_bounds__(kR3Threads) void k_replay_ref4(Mailbox mb0, u64 occ
       }
     };
     u32 ply = 0;
-    if (LOOK) nx = tab(move_of(buf[0]));
-    for (; ply + PF <= n_plies; ply += PF) {
+    for (; ply + kR4Prefetch <= n_plies; ply += kR4Prefetch) {
       const u32 s0 = ply & 63;
 #pragma unroll
-      for (int k = 0; k < PF; ++k) {
+      for (int k = 0; k < kR4Prefetch; ++k) {
         const u32 m = move_of(buf[k]);
-        buf[k] = load_move(ply + PF + k);
-        ply_step(m, s0 + k, LOOK ? move_of(buf[(k + 1) % PF]) : 0u, ply + k);  // k = PF - 1: ply + PF, reloaded at k = 0
+        buf[k] = load_move(ply + kR4Prefetch + k);
+        ply_step(m, s0 + k, ply + k);
       }
-      if (((ply + PF) & 63) == 0) flush(ply + PF - 64, 64);
+      if (((ply + kR4Prefetch) & 63) == 0) flush(ply + kR4Prefetch - 64, 64);
     }
 #pragma unroll
-    for (int k = 0; k < PF - 1; ++k)
-      if (ply + k < n_plies) ply_step(move_of(buf[k]), (ply + k) & 63, LOOK ? move_of(buf[k + 1]) : 0u, ply + k);
+    for (int k = 0; k < kR4Prefetch - 1; ++k)
+      if (ply + k < n_plies) ply_step(move_of(buf[k]), (ply + k) & 63, ply + k);
     if ((n_plies & 63) != 0) flush(n_plies & ~63u, n_plies & 63);
     accepted += nacc;  // a wave-level count: only the block sum is used
     if (lane == 0) validated += nvalw;  // wave-level count, added once per wave
@@ -613,88 +605,6 @@ __global__ __launch_bounds__(kR3Threads) void k_replay_ref4(Mailbox mb0, u64 occ
 }
 
 // --------------------------------------------------------------- generator
-// k-th accepted move in (from, to) order: own pieces by ascending square, each
-// piece's targets ascending.
-__device__ __forceinline__ u32 ref_kth_move(const Board& b, u32 stm, u32 k) {
-  const u64 occ = occupied(b);
-  u64 own = stm ? b.b0 : (occ & ~b.b0);
-  while (own) {
-    const int f = lsb(own);
-    own &= own - 1;
-    const u64 t = ref_piece_targets(b, f, stm, nibble(b, f) >> 1);
-    const u32 c = pc(t);
-    if (k < c) return (u32)f | ((u32)select_bit(t, k) << 6);
-    k -= c;
-  }
-  return 0xFFFFu;  // unreachable when k < count
-}
-
-// K5, round 2.  The k-th move in (from, to) order without a per-piece loop:
-// every lane evaluates its position in the side-to-move view (white_view), so
-// one code path serves lanes of either colour; the source square of the k-th
-// move is found by a 6-step binary search over square prefixes, each step a
-// source-restricted bulk count (ref_count_from; prefix masks are built in real
-// square order and flipped into the view), and its target is the kk-th set bit
-// of that one piece's target set (ref_piece_targets_w).  The round-1 kernel
-// (k_gen_games_ref_v1: a per-piece loop with a per-kind switch) issued 3,842
-// VALU per wave and ply with 22 % of lanes active.  Same games, bit for bit
-// (tests/golden: C4 moves SHA-256).
-#ifdef DC_AB_KNOBS  // round-2 generator, kept for A/B measurement only (DC_GEN=2)
-__global__ __launch_bounds__(256) void k_gen_games_ref_v2(u64 seed, u64 first_game, u32 n_games, u32 n_plies,
-                                                          u32 noise_per_256, uint16_t* __restrict__ out) {
-  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_games) return;
-  u64 s = seed ^ (first_game + g);
-  Board b{0, 0, 0, 0};
-  startpos_board(b);
-  u32 stm = 0;
-  bool over = false;
-  for (u32 ply = 0; ply < n_plies; ++ply) {
-    uint16_t* slot = out + (size_t)ply * n_games + g;
-    const Board w = view_sel(b, stm);
-    const u32 flip = stm ? 56u : 0u;
-    const Sides sw = sides<0>(w);
-    const Props pr = make_props(sw.empty);
-    const u32 n = over ? 0u : ref_count_from_w(sw, pr, ~0ull);
-    over = n == 0;
-    u64 r = 0;
-    if (!over) r = splitmix_next(s);
-    const bool noise = (u32)(r & 0xFF) < noise_per_256;
-    // the k-th move of the (from, to)-ordered list.  Own pieces in real square
-    // order p_0 < p_1 < ...; c(j) = #moves of p_0..p_{j-1}.  Games start at
-    // startpos and REF never adds a piece, so there are at most 16: four
-    // halving steps find the largest j with c(j) <= k.
-    const u32 k = (u32)(((r >> 32) * (u64)n) >> 32);
-    const u64 occ = occupied(b);
-    const u64 own = stm ? b.b0 : (occ & ~b.b0);
-    const u32 np = (u32)__popcll(own);
-    u32 lo = 0, clo = 0;
-#pragma unroll
-    for (u32 step = 8; step; step >>= 1) {
-      const u32 mid = lo + step;
-      const u64 real = mid < np ? ((1ull << select_bit_bf(own, mid)) - 1) : ~0ull;
-      const u64 view = stm ? flip_rows(real) : real;
-      const u32 c = (over || mid >= np) ? 0xFFFFFFFFu : ref_count_from_w(sw, pr, view);
-      if (c <= k) {
-        lo = mid;
-        clo = c;
-      }
-    }
-    const u32 f = over ? 0u : select_bit_bf(own, lo);
-    const u64 tv = ref_piece_targets_w(w, (int)(f ^ flip));
-    const u64 treal = stm ? flip_rows(tv) : tv;
-    const u32 kth = (n && k - clo < (u32)__popcll(treal)) ? (f | (select_bit_bf(treal, k - clo) << 6)) : 0u;
-    const u32 m = noise ? (u32)((r >> 8) & 0xFFF) : kth;
-    *slot = over ? (uint16_t)0xFFFF : (uint16_t)m;
-    const bool ok = !over && (!noise || ref_verdict(b, stm, m) == V_OK);
-    if (ok) {
-      ref_make(b, (int)(m & 63), (int)((m >> 6) & 63));
-      stm ^= 1;
-    }
-  }
-}
-#endif  // DC_AB_KNOBS
-
 // K5, round 3 (k_gen_games_ref).  The same games as round 2 (the k-th move in
 // (from, to) order of real squares; C4's moves SHA-256 is the check), with
 // the per-ply work restructured so that no source-restricted bulk count is
@@ -825,7 +735,7 @@ __global__ __launch_bounds__(256, kGenMinWaves) void k_gen_games_ref(u64 seed, u
     const Sides sw = sides<0>(w);
     const u64 E = sw.empty, no = sw.notown, occ = sw.occ;
     const u64 occF = flip_rows(occ), noF = flip_rows(no);  // the board with its rows swapped
-    // pawn sources per direction class (ref_count_from_w's pawn terms)
+    // pawn sources per direction class (ref_count<0>'s pawn terms)
     const u64 S1 = sw.P & sh<-8>(E);
     const u64 S2 = S1 & kRow(1) & sh<-16>(E);
     const u64 SL = sw.P & sh<-7>(sw.enemy & kNotH);
@@ -955,41 +865,6 @@ __global__ __launch_bounds__(256, kGenMinWaves) void k_gen_games_ref(u64 seed, u
     }
   }
 }
-
-#ifdef DC_AB_KNOBS  // round-1 generator, kept for A/B measurement only (DC_GEN=1)
-__global__ __launch_bounds__(256) void k_gen_games_ref_v1(u64 seed, u64 first_game, u32 n_games, u32 n_plies,
-                                                          u32 noise_per_256, uint16_t* __restrict__ out) {
-  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_games) return;
-  u64 s = seed ^ (first_game + g);
-  Board b{0, 0, 0, 0};
-  startpos_board(b);
-  u32 stm = 0;
-  bool over = false;
-  for (u32 ply = 0; ply < n_plies; ++ply) {
-    uint16_t* slot = out + (size_t)ply * n_games + g;
-    if (over) {
-      *slot = 0xFFFF;
-      continue;
-    }
-    const u32 n = ref_count_rt(b, stm);
-    if (n == 0) {
-      over = true;
-      *slot = 0xFFFF;
-      continue;
-    }
-    const u64 r = splitmix_next(s);
-    u32 m;
-    if ((u32)(r & 0xFF) < noise_per_256) m = (u32)((r >> 8) & 0xFFF);
-    else m = ref_kth_move(b, stm, (u32)(((r >> 32) * (u64)n) >> 32));
-    *slot = (uint16_t)m;
-    if (ref_verdict(b, stm, m) == V_OK) {
-      ref_make(b, (int)(m & 63), (int)((m >> 6) & 63));
-      stm ^= 1;
-    }
-  }
-}
-#endif  // DC_AB_KNOBS
 
 // ------------------------------------------------------------- FIDE (K1/K2/K5)
 __global__ __launch_bounds__(256) void k_validate_fide(const DevPos* __restrict__ pos, const uint16_t* __restrict__ moves,
@@ -1251,16 +1126,6 @@ hipError_t launch_apply_ref(hipStream_t st, DevPos* pos, const uint16_t* moves, 
 // persistent grid is far smaller than k_replay_ref's).
 u32 replay_partials(u32 n_games) { return blocks_for(n_games, 256); }
 
-// DC_REPLAY=1 selects the arithmetic k_replay_ref (ref_verdict per ply, as the
-// validate kernels) instead of the LDS-table k_replay_ref3, for A/B and parity.
-static bool replay_arith() {
-  static const bool v = [] {
-    const char* e = ab_env("DC_REPLAY");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-
 static u32 replay3_grid(u32 n_games) {
   static const u32 resident = [] {
     int per_cu = 0, dev = 0, cus = 0;
@@ -1294,7 +1159,7 @@ hipError_t launch_replay_ref(hipStream_t st, const Board& start, u32 stm0, const
     if ((u64)n_games * n_plies * 2 > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const u32 nb = replay3_grid(n_games);
     const bool dw = (n_games & 1) == 0;
-    auto ki = dw ? k_replay_ref4<0, 4, true, true> : k_replay_ref4<0, 4, false, true>;
+    auto ki = dw ? k_replay_ref4<true, true> : k_replay_ref4<false, true>;
     hipLaunchKernelGGL(ki, dim3(nb), dim3(kR3Threads), 0, st, host_mailbox(start), start.b1 | start.b2 | start.b3,
                        stm0, moves, n_games, n_plies, bitmap, digests, partial, info, boards);
     hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(256), 0, st, partial, nb, stats, stats_host);
@@ -1302,27 +1167,15 @@ hipError_t launch_replay_ref(hipStream_t st, const Board& start, u32 stm0, const
     return hipGetLastError();
   }
   // n_plies == 0 (no moves buffer to clamp loads into) takes k_replay_ref
-  if (n_plies > 0 && !replay_arith()) {
+  if (n_plies > 0) {
     const u32 nb = replay3_grid(n_games);
     // k_replay_ref4 addresses the whole move array through one buffer
-    // descriptor (32-bit offsets); larger batches, and DC_REPLAY=3 in the A/B
-    // build, take k_replay_ref3's per-row descriptors
-    static const bool force3 = [] {
-      const char* e = ab_env("DC_REPLAY");
-      return e && e[0] == '3';
-    }();
-    // A/B: DC_REPLAY=41 -> with the table lookahead, =42 -> u16 move loads,
-    // =48 -> 8-ply move prefetch (round 2: 0.98 vs 0.88 ms for 4 plies)
-    static const int v4 = [] {
-      const char* e = ab_env("DC_REPLAY");
-      return (e && e[0] == '4') ? atoi(e) : 0;
-    }();
-    const bool dw = (n_games & 1) == 0 && v4 != 42;
-    auto k4 = dw ? k_replay_ref4<0, 4, true> : k_replay_ref4<0, 4, false>;
-    if (v4 == 41) k4 = dw ? k_replay_ref4<1, 4, true> : k_replay_ref4<1, 4, false>;
-    if (v4 == 48) k4 = dw ? k_replay_ref4<0, 8, true> : k_replay_ref4<0, 8, false>;
+    // descriptor (32-bit offsets); larger batches take k_replay_ref3's per-row
+    // descriptors
+    const bool dw = (n_games & 1) == 0;
+    auto k4 = dw ? k_replay_ref4<true> : k_replay_ref4<false>;
     const bool fits = (u64)n_games * n_plies * 2 <= 0xFFFFFFFFull;
-    if (fits && !force3)
+    if (fits)
       hipLaunchKernelGGL(k4, dim3(nb), dim3(kR3Threads), 0, st, host_mailbox(start), start.b1 | start.b2 | start.b3,
                          stm0, moves, n_games, n_plies, bitmap, digests, partial, nullptr, nullptr);
     else
@@ -1343,22 +1196,8 @@ hipError_t launch_replay_ref(hipStream_t st, const Board& start, u32 stm0, const
 hipError_t launch_gen_games_ref(hipStream_t st, u64 seed, u64 first_game, u32 n_games, u32 n_plies, u32 noise,
                                 uint16_t* out) {
   if (n_games == 0) return hipSuccess;
-#ifdef DC_AB_KNOBS
-  // DC_GEN=1 / 2 (A/B build only): the round-1 / round-2 generators
-  static const bool v1 = [] {
-    const char* e = ab_env("DC_GEN");
-    return e && e[0] == '1';
-  }();
-  static const bool v2 = [] {
-    const char* e = ab_env("DC_GEN");
-    return e && e[0] == '2';
-  }();
-  auto kg = v1 ? k_gen_games_ref_v1 : v2 ? k_gen_games_ref_v2 : k_gen_games_ref;
-#else
-  auto kg = k_gen_games_ref;
-#endif
-  hipLaunchKernelGGL(kg, dim3(blocks_for(n_games, 256)), dim3(256), 0, st, seed, first_game, n_games, n_plies, noise,
-                     out);
+  hipLaunchKernelGGL(k_gen_games_ref, dim3(blocks_for(n_games, 256)), dim3(256), 0, st, seed, first_game, n_games,
+                     n_plies, noise, out);
   return hipGetLastError();
 }
 

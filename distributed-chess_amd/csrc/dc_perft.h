@@ -71,7 +71,6 @@ hipError_t launch_level_write(hipStream_t st, u32 rules, int stm, const Board* n
                               const uint16_t* tags, const Range* rng, u64 n_bound, const u32* counts,
                               const u64* chunk_base, Board* out, uint16_t* out_meta, uint16_t* out_tags, u64 cap,
                               u32* next_counts = nullptr, u64* next_sum = nullptr);
-hipError_t launch_slice(hipStream_t st, Range* rng, u32 shard, u32 n_shards);
 // out[0..256) = the run's divide (0 past n_root), out[256] = n_root | overflow << 32,
 // out[257] = the total: one run's result kept on the device (dc_perft_repeat_device).
 // The destination is read from a device-side cursor {base, run index} that the

@@ -16,7 +16,7 @@
 //     k_level_write     the children written (and, optionally, counted)
 //   the shard of a level (dc_perft_shard)
 //     k_gather_shard    every n-th node, copied;  k_shard_range  the same over
-//                       move words, size only;  k_slice  a contiguous part (A/B)
+//                       move words, size only
 //   the final stage
 //     k_count1          the last ply alone (depth 2)
 //     k_count2b         the last two plies, 256 parents per block (FIDE)
@@ -1407,11 +1407,6 @@ __global__ void k_wide_slice(const Range* __restrict__ lvl, const u64* __restric
   *counter = 0;
 }
 
-__global__ void k_slice(Range* rng, u32 shard, u32 n_shards) {
-  const u64 lo = rng->lo, n = rng->hi - rng->lo;
-  *rng = Range{lo + n * shard / n_shards, lo + n * (shard + 1) / n_shards};
-}
-
 // Strided shard of a level: nodes lo + shard, lo + shard + n_shards, ... are
 // gathered to the front of `out` and the level's Range becomes [0, count).
 // Subtree sizes vary along the frontier (a contiguous eighth of ply 3 held
@@ -1620,7 +1615,7 @@ __global__ __launch_bounds__(256, R::kFinalMinBlocks) void k_count2b(const Board
 
 // ---------------------------------------------------- k_count2c (REF final stage)
 // The last two plies under RULES_REF with the quiet-move shortcut of
-// ref_count_nonpawn: per parent P (side S to move, opponent O) the block first
+// ref_count_nonpawn_g: per parent P (side S to move, opponent O) the block first
 // computes base = O's knight/king/slider moves in P and att = O's slider rays.
 // A child reached by a quiet move f -> t with f, t outside att then has
 //     count_O(child) = base + O's pawn moves in the child      (~40 VALU ops)
@@ -1644,7 +1639,7 @@ constexpr int kC2cQueue = 128;
 // the rest keep the full recount.
 // The parent split keeps the side to move's eight slider target sets (its own
 // fills) for the first window's enumeration of the special moves, which
-// otherwise would run the same eight fills again (REUSE in c2c_group).
+// otherwise would run the same eight fills again (tgt in c2c_group).
 struct alignas(8) C2cRec {
   u64 b0, b1, b2, b3, att, orth;
   u32 base;
@@ -1710,25 +1705,20 @@ __device__ __forceinline__ u32 c2c_diag(const C2cShared<CAP>& sh, u32 e) {
   return ref_count_child_diag<1 - STM>(sh.board(pl), (int)(e & 63), (int)((e >> 6) & 63), sh.basec(pl) - sh.diagc(pl));
 }
 
-// BULK: children reached by "simple" moves -- quiet, f and t off the
+// The bulk split: children reached by "simple" moves -- quiet, f and t off the
 // opponent's slider rays and off its pawn-sensitive squares G
 // (ref_pawn_planes) -- all have count_O = base + pawn_O(parent), so they are
 // counted per parent as n_simple x (base + pawn_O) and never enumerated; only
 // the other ("special") children go through the LDS slots.
-// PHASE (timing experiments only; wrong counts unless 0): 1 skips the children,
-// 2 also skips the enumeration, leaving the per-parent counts; 5 skips the
-// full recounts (queued children still drained), 6 also the quiet children's
-// pawn counts; 7 replaces the counts by statistics (tools/c2c_stats.py);
-// 8 is 0 plus a per-block timeline (tools/c2c_trace.py).  Phases other
-// than 0 are instantiated only in the A/B build (-DDC_AB_KNOBS, libdchess_ab.so).
 // One group of 256 parents (one per thread; `valid` false for an empty slot):
-// the last two plies below each, added into the block's divide histogram.
+// the last two plies below each, added into the block's divide histogram
+// (sh.hist, which the calling kernel flushes).
 // Called by k_count2c (parents read from a level in HBM) and k_perft_dfs
 // (parents produced by each lane's DFS stack).  Block-uniform call; ends with
 // a block barrier (par/att/ptag/slot are reused by the next group).
 // PARSUM (k_count3c<.., DEDUP>): the leaves are summed per parent instead, in
 // sh.sums (which overlays sh.hist), and the caller takes sums[its own thread]
-// after the closing barrier; `tag`, hist and divide are not used.  A child's
+// after the closing barrier; `tag` and hist are not used.  A child's
 // count goes to sums[pl] with one 32-bit LDS add (pl, the parent's thread, is
 // in every slot and queue entry; a parent has at most 218 x 218 leaves), where
 // the histogram needs the record's tag, a compare with tag0 and, for every tag
@@ -1736,48 +1726,34 @@ __device__ __forceinline__ u32 c2c_diag(const C2cShared<CAP>& sh, u32 e) {
 // addresses when the tags are grandparents (about 11 to a group).  The parent's
 // own lane stores its simple children's leaves before the first barrier, which
 // also re-initialises its entry for this group.
-template <int STM, u32 CAP, int PHASE = 0, bool BULK = true, bool PARSUM = false>
-__device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const Board& p, u32 tag,
-                                          u64* __restrict__ divide, u32 wave) {
-  static_assert(!PARSUM || (PHASE == 0 && BULK), "per-parent sums: the bulk split, counting");
+template <int STM, u32 CAP, bool PARSUM = false>
+__device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const Board& p, u32 tag, u32 wave) {
   // wave: this wave's index in the block (an SGPR, readfirstlane at kernel
   // entry); the thread index is rebuilt where it is used (otid)
   const u32 w = wave, lane = lane_id();
-  // GQ: the group-wise recount queue, in the bulk split
-  constexpr bool GQ = BULK;
+  // the three per-wave queues: full recounts, group-wise recounts, and the
+  // quiet special children (their pawn recount, 64 at a time)
   u32* q = sh.queue[w];
   static_assert(offsetof(C2cShared<CAP>, queue_d) == offsetof(C2cShared<CAP>, queue) + sizeof(sh.queue),
                 "queue_d must follow queue");
   u32* qd = sh.queue_d[w];
-  // QQ: the quiet special children's queue (their pawn recount, 64 at a time)
-  constexpr bool QQ = GQ;
   u32* qq = sh.queue_q[w];
   u32 qnq = 0;
   u32 cnt = 0, base = 0, diag = 0;
   u64 att = 0, orth = 0, Fs = 0, Ts = 0, simple_leaves = 0;
-  u32 nsim = 0;
-  constexpr bool REUSE = GQ;
-  u64 tgt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (REUSE) slider target sets, compile-time indexed
+  u64 tgt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the split's slider target sets, compile-time indexed
   if constexpr (!PARSUM) sh.put_tag(otid(w), tag);  // (the previous group ended with a barrier)
   if (valid) {
-    if constexpr (BULK) {
-      ParentSplit ps;
-      ref_parent_split<STM, GQ, REUSE>(p, ps, tgt);
-      base = ps.base;
-      att = ps.att;
-      if constexpr (GQ) {
-        orth = ps.orth;
-        diag = ps.diag;
-      }
-      Fs = ps.Fs;
-      Ts = ps.Ts;
-      cnt = ps.n_total - ps.n_simple;  // enumerated (special) children only
-      simple_leaves = (u32)(ps.n_simple * (ps.base + ps.pawn_o) + ps.gcorr);  // (>= 0: a sum of child counts)
-      nsim = ps.n_simple;
-    } else {
-      cnt = ref_count<STM>(p);
-      base = ref_count_nonpawn<1 - STM>(p, att);
-    }
+    ParentSplit ps;
+    ref_parent_split<STM>(p, ps, tgt);
+    base = ps.base;
+    att = ps.att;
+    orth = ps.orth;
+    diag = ps.diag;
+    Fs = ps.Fs;
+    Ts = ps.Ts;
+    cnt = ps.n_total - ps.n_simple;  // enumerated (special) children only
+    simple_leaves = (u32)(ps.n_simple * (ps.base + ps.pawn_o) + ps.gcorr);  // (>= 0: a sum of child counts)
   }
   // (PARSUM: this thread's entry was last read by this thread, after the
   // previous group; the other threads' adds into it come after the scan's barrier)
@@ -1794,7 +1770,6 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   auto key = [&](u32 pl) { return PARSUM ? pl : sh.tag(pl); };
   // k leaves under the key `ptag`
   auto add_tag = [&](u32 ptag, u32 k, bool live) {
-    if constexpr (PHASE == 7) return;
     if (!live) return;
     if constexpr (PARSUM) {
       atomicAdd(&sh.sums[ptag], k);
@@ -1806,83 +1781,47 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   auto add = [&](u32 pl, u32 k, bool live) { add_tag(key(pl), k, live); };
   u32 qn = 0, qnd = 0;  // queue lengths: wave-uniform (kept scalar via readfirstlane)
   // One candidate child: its parent's LDS record is loaded first (so two
-  // candidates' loads can be in flight together), then the short path if the
-  // move is quiet, else the child is appended to a queue: the group-wise one
-  // (GQ) if the move is off the opponent's orthogonal group, else the full one.
+  // candidates' loads can be in flight together), then the child is appended
+  // to a queue: the quiet one if the move is quiet, else the group-wise one if
+  // the move is off the opponent's orthogonal group, else the full one.
   struct Cand {
-    u32 e, base, tag;
+    u32 e;
     Board pb;
     u64 a, o;
   };
   auto fetch = [&](u32 e) {
     const u32 pl = e >> 15;
-    // the whole 56-byte record: board, rays, orthogonal group, base/tag/diag
-    return Cand{e, sh.basec(pl), sh.tag(pl), sh.board(pl), sh.rays(pl), GQ ? sh.orth(pl) : 0ull};
+    // the record's board, rays and orthogonal group (its counts and tag are read by the drains)
+    return Cand{e, sh.board(pl), sh.rays(pl), sh.orth(pl)};
   };
   auto consume = [&](const Cand& c, bool live) {
     const int f = (int)(c.e & 63), t = (int)((c.e >> 6) & 63);
     const u64 occ = occupied(c.pb);
     const bool quiet = ((((occ | c.a) >> t) | (c.a >> f)) & 1) == 0;
-    if constexpr (QQ) {
-      const u64 qmask = ballot(live && quiet);
-      if (live && quiet) qq[qnq + mask_rank(qmask)] = c.e;
-      qnq = __builtin_amdgcn_readfirstlane(qnq + (u32)__popcll(qmask));
-    } else {
-      if (live && quiet) add_tag(c.tag, c.base + (PHASE == 6 ? (u32)t : ref_pawn_count_child<1 - STM>(c.pb, f, t)), true);
-    }
+    const u64 qmask = ballot(live && quiet);
+    if (live && quiet) qq[qnq + mask_rank(qmask)] = c.e;
+    qnq = __builtin_amdgcn_readfirstlane(qnq + (u32)__popcll(qmask));
     const bool full = live && !quiet;
     const u64 em = ballot(full);
-    if constexpr (PHASE == 7) {  // statistics: divide[0] quiet special children, [1] full-recount children
-      const u64 qm = ballot(live && quiet);
-      if (lane == 0) {
-        atomicAdd((unsigned long long*)divide, (unsigned long long)__popcll(qm));
-        atomicAdd((unsigned long long*)(divide + 1), (unsigned long long)__popcll(em));
-      }
-      // full children by the opponent O's slider group whose rays the move
-      // changes: [4] captures, [5] orthogonal only, [6] diagonal only, [7] both, [8] neither
-      const Sides so = sides<1 - STM>(c.pb);
-      const u64 e = so.empty;
-      const u64 ao = ray_attacks<8, kAll>(so.O, e) | ray_attacks<-8, kAll>(so.O, e) | ray_attacks<1, kNotA>(so.O, e) |
-                     ray_attacks<-1, kNotH>(so.O, e);
-      const u64 ad = ray_attacks<9, kNotA>(so.D, e) | ray_attacks<-9, kNotH>(so.D, e) | ray_attacks<7, kNotH>(so.D, e) |
-                     ray_attacks<-7, kNotA>(so.D, e);
-      const u64 ft = (1ull << f) | (1ull << t);
-      const bool capt = (occ >> t) & 1;
-      const bool go = (ao & ft) || ((so.O >> t) & 1), gd = (ad & ft) || ((so.D >> t) & 1);
-      const u64 m4 = ballot(full && capt), m5 = ballot(full && go && !gd), m6 = ballot(full && gd && !go);
-      const u64 m7 = ballot(full && go && gd), m8 = ballot(full && !go && !gd);
-      if (lane == 0) {
-        atomicAdd((unsigned long long*)(divide + 4), (unsigned long long)__popcll(m4));
-        atomicAdd((unsigned long long*)(divide + 5), (unsigned long long)__popcll(m5));
-        atomicAdd((unsigned long long*)(divide + 6), (unsigned long long)__popcll(m6));
-        atomicAdd((unsigned long long*)(divide + 7), (unsigned long long)__popcll(m7));
-        atomicAdd((unsigned long long*)(divide + 8), (unsigned long long)__popcll(m8));
-      }
+    const bool go = ((((c.o >> t) | (c.o >> f)) & 1) != 0);
+    const u64 ef = ballot(full && go), ed = em ^ ef;
+    if (full) {
+      // one store through a selected address; the ranks from v_mbcnt on the
+      // SGPR masks (round 4: 20 -> 8 VALU per candidate, tools/bbprof.py)
+      // (qd = q + kQd: sh.queue_d follows sh.queue, so one base address)
+      constexpr u32 kQd = sizeof(sh.queue) / sizeof(u32);
+      u32 rf = mask_rank(ef), rd = mask_rank(ed);
+      asm("" : "+v"(rf), "+v"(rd));  // both ranks, then one select (not a select of the masks)
+      q[go ? qn + rf : kQd + qnd + rd] = c.e;
     }
-    if constexpr (GQ) {
-      const bool go = ((((c.o >> t) | (c.o >> f)) & 1) != 0);
-      const u64 ef = ballot(full && go), ed = em ^ ef;
-      if (full) {
-        // one store through a selected address; the ranks from v_mbcnt on the
-        // SGPR masks (round 4: 20 -> 8 VALU per candidate, tools/bbprof.py)
-        // (qd = q + kQd: sh.queue_d follows sh.queue, so one base address)
-        constexpr u32 kQd = sizeof(sh.queue) / sizeof(u32);
-        u32 rf = mask_rank(ef), rd = mask_rank(ed);
-        asm("" : "+v"(rf), "+v"(rd));  // both ranks, then one select (not a select of the masks)
-        q[go ? qn + rf : kQd + qnd + rd] = c.e;
-      }
-      qn = __builtin_amdgcn_readfirstlane(qn + (u32)__popcll(ef));
-      qnd = __builtin_amdgcn_readfirstlane(qnd + (u32)__popcll(ed));
-    } else {
-      if (full) q[qn + mask_rank(em)] = c.e;
-      qn = __builtin_amdgcn_readfirstlane(qn + (u32)__popcll(em));
-    }
+    qn = __builtin_amdgcn_readfirstlane(qn + (u32)__popcll(ef));
+    qnd = __builtin_amdgcn_readfirstlane(qnd + (u32)__popcll(ed));
   };
   auto drain64 = [&]() {  // qn >= 64: recount 64 queued children in full
     wave_lds_sync();
     const u32 e2 = q[lane];
     const u32 tg = key(e2 >> 15);  // issued with the record reads
-    add_tag(tg, PHASE == 5 || PHASE == 6 ? e2 & 1 : c2c_full<STM>(sh, e2), true);
+    add_tag(tg, c2c_full<STM>(sh, e2), true);
     wave_lds_sync();
     if (lane + 64 < qn) q[lane] = q[lane + 64];
     qn = __builtin_amdgcn_readfirstlane(qn - 64);
@@ -1891,7 +1830,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
     wave_lds_sync();
     const u32 e2 = qd[lane];
     const u32 tg = key(e2 >> 15);
-    add_tag(tg, PHASE == 5 || PHASE == 6 ? e2 & 1 : c2c_diag<STM>(sh, e2), true);
+    add_tag(tg, c2c_diag<STM>(sh, e2), true);
     wave_lds_sync();
     if (lane + 64 < qnd) qd[lane] = qd[lane + 64];
     qnd = __builtin_amdgcn_readfirstlane(qnd - 64);
@@ -1900,7 +1839,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   auto quiet_count = [&](u32 e2) -> u32 {
     const u32 pl = e2 >> 15;
     const int f = (int)(e2 & 63), t = (int)((e2 >> 6) & 63);
-    return sh.basec(pl) + (PHASE == 6 ? (u32)t : ref_pawn_count_child<1 - STM>(sh.board(pl), f, t));
+    return sh.basec(pl) + ref_pawn_count_child<1 - STM>(sh.board(pl), f, t);
   };
   auto drain64q = [&]() {  // qnq >= 64: 64 queued quiet children
     wave_lds_sync();
@@ -1913,45 +1852,29 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   };
   auto drain = [&]() {
     if (qn >= 64) drain64();
-    if constexpr (GQ) if (qnd >= 64) drain64d();
-    if constexpr (QQ) if (qnq >= 64) drain64q();
+    if (qnd >= 64) drain64d();
+    if (qnq >= 64) drain64q();
   };
-  if constexpr (BULK && PHASE != 7 && !PARSUM) add(otid(w), (u32)simple_leaves, valid);
-  if constexpr (PHASE == 7) {  // [2] simple children, [3] parents
-    const u64 ns = wave_sum64(nsim), np = __popcll(ballot(valid));
-    if (lane == 0) {
-      atomicAdd((unsigned long long*)(divide + 2), (unsigned long long)ns);
-      atomicAdd((unsigned long long*)(divide + 3), (unsigned long long)np);
-    }
-  }
-  if constexpr (PHASE == 1 || PHASE == 2) acc += cnt + base + (u32)att;
-  for (u32 wbase = 0; wbase < (PHASE == 2 ? 0u : total); wbase += CAP) {
+  if constexpr (!PARSUM) add(otid(w), (u32)simple_leaves, valid);
+  for (u32 wbase = 0; wbase < total; wbase += CAP) {
     if (wbase) __syncthreads();  // previous window fully read
-    // each (f, t) of this parent's enumerated (BULK: special) moves -> visit(f, t)
-    // the parent is read back from its record (after the barrier: a fresh
-    // LDS read), so its board is not live across the consume/drain loop
-    // (GQ) and the simple-move masks rebuilt from it and its rays
-    // (ref_parent_split's keep), so neither is live across the loop
+    // each (f, t) of this parent's special moves -> visit(f, t).  The parent
+    // is read back from its record (after the barrier: a fresh LDS read), so
+    // its board is not live across the consume/drain loop.
     auto each_move = [&](auto&& visit) {
-      if constexpr (REUSE) {
-        if (wbase == 0) {  // the norm: the split's masks and fills are still live
-          ref_for_each_special_pre<STM>(sh.board(otid(w)), Fs, Ts, tgt, visit);
-          return;
-        }
+      if (wbase == 0) {  // the norm: the split's masks and fills are still live
+        ref_for_each_special_pre<STM>(sh.board(otid(w)), Fs, Ts, tgt, visit);
+        return;
       }
-      if constexpr (GQ) {
-        const Board pp = sh.board(otid(w));
-        u32 unused;
-        const u64 rays = sh.rays(otid(w));
-        const u64 occ = occupied(pp), own = STM ? pp.b0 : (occ & ~pp.b0);
-        u64 p1, n1, big;
-        const u64 g = ref_pawn_planes<1 - STM>(pp, unused, p1, n1, big);
-        ref_for_each_special<STM>(pp, own & ~(rays | g), ~(occ | rays | big), visit);
-      } else if constexpr (BULK) {
-        ref_for_each_special<STM>(p, Fs, Ts, visit);
-      } else {
-        ref_for_each_move<STM>(p, visit);
-      }
+      // a later window: the simple-move masks rebuilt from the record's board
+      // and rays, so neither is live across the loop
+      const Board pp = sh.board(otid(w));
+      u32 unused;
+      const u64 rays = sh.rays(otid(w));
+      const u64 occ = occupied(pp), own = STM ? pp.b0 : (occ & ~pp.b0);
+      u64 p1, n1, big;
+      const u64 g = ref_pawn_planes<1 - STM>(pp, unused, p1, n1, big);
+      ref_for_each_special<STM>(pp, own & ~(rays | g), ~(occ | rays | big), visit);
     };
     const u32 pl15 = otid(w) << 15;
     if (total <= CAP) {  // the norm: one window, no range checks
@@ -1969,7 +1892,7 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
     __syncthreads();
     const u32 nslots = min(CAP, total - wbase);
     // two slots per lane per step, loaded together, so the LDS round trips overlap
-    u32 r0 = (PHASE == 1 || PHASE == 2) ? nslots : w * 64;
+    u32 r0 = w * 64;
     for (; r0 + 256 < nslots; r0 += 512) {
       const u32 ra = r0 + lane, rb = r0 + 256 + lane;
       const bool lb = rb < nslots;
@@ -1999,8 +1922,8 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
     __syncthreads();  // every wave is past its last slot read: the slot area is free
     if (lane == 0) {
       cnt[w] = qn;
-      cnt[4 + w] = GQ ? qnd : 0u;
-      cnt[8 + w] = QQ ? qnq : 0u;
+      cnt[4 + w] = qnd;
+      cnt[8 + w] = qnq;
     }
     __syncthreads();
     u32 of = 0, od = 0, oq = 0, nf = 0, nd = 0, nq = 0;
@@ -2018,8 +1941,8 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
     nd = __builtin_amdgcn_readfirstlane(nd);
     nq = __builtin_amdgcn_readfirstlane(nq);
     if (lane < qn) sh.slot[of + lane] = q[lane];
-    if (GQ && lane < qnd) sh.slot[nf + od + lane] = qd[lane];
-    if (QQ && lane < qnq) sh.slot[nf + nd + oq + lane] = qq[lane];
+    if (lane < qnd) sh.slot[nf + od + lane] = qd[lane];
+    if (lane < qnq) sh.slot[nf + nd + oq + lane] = qq[lane];
     __syncthreads();
     const u32 cf = (nf + 63) / 64, cd = (nd + 63) / 64, cq = (nq + 63) / 64;
     for (u32 c = w; c < cf + cd + cq; c += 4) {
@@ -2028,9 +1951,9 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
       const bool live = k < (kind == 0 ? nf : kind == 1 ? nf + nd : nf + nd + nq);
       const u32 e2 = live ? sh.slot[k] : 0u;
       u32 r = 0;
-      if (kind == 0) r = live ? (PHASE == 5 || PHASE == 6 ? e2 & 1 : c2c_full<STM>(sh, e2)) : 0u;
-      else if (kind == 1) r = live ? (PHASE == 5 || PHASE == 6 ? e2 & 1 : c2c_diag<STM>(sh, e2)) : 0u;
-      else if (QQ) r = live ? quiet_count(e2) : 0u;
+      if (kind == 0) r = live ? c2c_full<STM>(sh, e2) : 0u;
+      else if (kind == 1) r = live ? c2c_diag<STM>(sh, e2) : 0u;
+      else r = live ? quiet_count(e2) : 0u;
       add(e2 >> 15, r, live);
     }
   }
@@ -2038,22 +1961,18 @@ __device__ __forceinline__ void c2c_group(C2cShared<CAP>& sh, bool valid, const 
   __syncthreads();  // par/att/ptag/slot reused by the next group (PARSUM: the sums are complete)
 }
 
-#ifdef DC_AB_KNOBS
-// PHASE 8 (A/B build): PHASE 0 plus a per-block timeline (wall clock, 100 MHz)
-// in g_c2c_trace, read back by dc_ab_c2c_trace (tools/c2c_trace.py).
-constexpr int kTraceWords = 8;
-constexpr int kTraceBlocks = 4096;
-__device__ u64 g_c2c_trace[kTraceBlocks * kTraceWords];
-#endif
-
-template <int STM, u32 CAP, int PHASE = 0, bool BULK = true, int MINW = 4>
-__global__ __launch_bounds__(256, MINW) void k_count2c(const Board* __restrict__ nodes, const uint16_t* __restrict__ tags,
-                                                 const Range* __restrict__ rng, u64* __restrict__ divide,
-                                                 u32* __restrict__ next_chunk) {
+// 4 blocks of 256 per CU (since round 2): 128 VGPRs with 52 B/lane of spills
+// then; 3: 140 VGPRs, no scratch.  perft(7) count2: 0.498-0.505 vs 0.523-0.532 ms
+// (round 2; round 1's body measured equal).  Two round-2 dead ends: 16 instead
+// of 24 slots per parent (LDS for 4 blocks per CU) measured the same, and a
+// chunk prefetch pipeline (next chunk's parents in registers across the group,
+// next index fetched a group ahead) was slower at either budget (0.542 /
+// 0.574 ms).
+template <int STM, u32 CAP>
+__global__ __launch_bounds__(256, 4) void k_count2c(const Board* __restrict__ nodes, const uint16_t* __restrict__ tags,
+                                              const Range* __restrict__ rng, u64* __restrict__ divide,
+                                              u32* __restrict__ next_chunk) {
   __shared__ C2cShared<CAP> sh;
-  constexpr int GP = PHASE == 8 ? 0 : PHASE;
-  [[maybe_unused]] u64 t_entry = 0, t_wait = 0, t_last = 0, n_chunks = 0;
-  if constexpr (PHASE == 8) t_entry = wall_clock64();
   tag_hist_init(sh.hist);
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool t0 = wave == 0 && lane_id() == 0;
@@ -2061,21 +1980,14 @@ __global__ __launch_bounds__(256, MINW) void k_count2c(const Board* __restrict__
   // Blocks take 256-parent chunks from a counter: the cost of a chunk varies
   // with its positions, and static ranges left the slowest block behind (a
   // sharded launch has only ~3 chunks per block).  The counter's round trips
-  // are 2.7 % of a block's lifetime at perft(7) (tools/c2c_trace.py).  Each
-  // block's first chunk is its own index (round 5, as k_count3c): the counter
-  // hands out the rest from gridDim.x on.
+  // were 2.7 % of a block's lifetime at perft(7) (a per-block timeline, round
+  // 2).  Each block's first chunk is its own index (round 5, as k_count3c):
+  // the counter hands out the rest from gridDim.x on.
   for (bool first = true;; first = false) {
-    [[maybe_unused]] u64 ta = 0;
-    if constexpr (PHASE == 8) ta = wall_clock64();
     if (t0) sh.next = first ? blockIdx.x : gridDim.x + atomicAdd(next_chunk, 1u);
     __syncthreads();
-    if constexpr (PHASE == 8) {
-      t_last = wall_clock64();
-      t_wait += t_last - ta;
-    }
     const u64 s = lo + (u64)sh.next * kChunk;
     if (s >= hi) break;  // block-uniform
-    if constexpr (PHASE == 8) ++n_chunks;
     const u64 i = s + otid(wave);
     const bool valid = i < hi;
     Board p{0, 0, 0, 0};
@@ -2084,26 +1996,9 @@ __global__ __launch_bounds__(256, MINW) void k_count2c(const Board* __restrict__
       p = load_board(nodes, i);
       tag = tags[i];
     }
-    c2c_group<STM, CAP, GP, BULK>(sh, valid, p, tag, divide, wave);
+    c2c_group<STM, CAP>(sh, valid, p, tag, wave);
   }
   tag_hist_flush(sh.hist, divide, otid(wave));
-#ifdef DC_AB_KNOBS
-  if constexpr (PHASE == 8) {
-    if (t0 && blockIdx.x < kTraceBlocks) {
-      u32 xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      u64* r = g_c2c_trace + blockIdx.x * kTraceWords;
-      r[0] = t_entry;
-      r[1] = wall_clock64();
-      r[2] = n_chunks;
-      r[3] = t_wait;
-      r[4] = xcc & 15;
-      r[5] = t_last;
-      r[6] = gridDim.x;
-      r[7] = 0;
-    }
-  }
-#endif
 }
 
 // ---------------------------------------- k_count3c (REF: the last three plies)
@@ -2189,7 +2084,7 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
       const u32 mv = (u32)e;
       ref_make(ch, (int)(mv & 63), (int)((mv >> 6) & 63));
     }
-    c2c_group<1 - STM_G, CAP, 0, true, DEDUP>(sh, valid, ch, tag, divide, wave);
+    c2c_group<1 - STM_G, CAP, DEDUP>(sh, valid, ch, tag, wave);
     // (c2c_group ended with a barrier: every thread is past its read of grp's state)
     if constexpr (DEDUP) {
       // This thread's parent's leaves (0 for an empty slot; the thread itself
@@ -2237,19 +2132,15 @@ __global__ __launch_bounds__(256, MINW) void k_count3c(const Board* __restrict__
 // kFoldCountWaves waves of the grid count a strided share of all records each:
 // one atomic per wave of the grid on each count cost ~20 us at 2,048 waves
 // (same-line device atomics pass one request at a time).
-// LDSH = false (A/B build only): no LDS at all, which would fit beside
-// k_count3c too -- the wave's distinct root tags are peeled off one at a time,
-// each with a wave sum and one global atomic.  Measured 38-40 us against 17 us
-// at every grid from 128 to 1,024 blocks:
-// ~4,000 one-lane atomics into the two cache lines of `divide`, where the
-// histogram's flush is one 20-lane atomic per block.
+// (A form without LDS, which would fit beside k_count3c too, measured 38-40 us
+// against 17 us at every grid from 128 to 1,024 blocks and was removed:
+// DESIGN.md section 3.9.)
 constexpr u32 kFoldGrid = 256;
 constexpr u32 kFoldCountWaves = 128;
-template <bool LDSH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(16))) void k_front_fold(const FrontDedup dd, const Board* __restrict__ out,
                                                     const Range* __restrict__ rng_out, PerftResult* __restrict__ res) {
-  [[maybe_unused]] __shared__ u64 hist[LDSH ? 256 : 1];
-  if constexpr (LDSH) tag_hist_init(hist);
+  __shared__ u64 hist[256];
+  tag_hist_init(hist);
   const u32 lane = lane_id();
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const u32 n_res = dd.st->n_rec;
@@ -2288,19 +2179,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(16))) void k_fr
     }
     if (own) dd.key[s] = 0;
     const u32 tag = fl & 255u;
-    if constexpr (LDSH) {
-      tag_hist_add(hist, tag, v, true);
-    } else {
-      u64 m = ballot(v != 0);
-      while (m) {  // wave-uniform: one round per distinct tag
-        const int leader = lsb(m);
-        const u32 tag0 = lane_bcast(tag, (u32)leader);
-        const bool mine = v != 0 && tag == tag0;
-        const u64 sum = wave_sum64(mine ? v : 0);
-        if ((int)lane == leader) atomicAdd((unsigned long long*)(res->divide + tag0), (unsigned long long)sum);
-        m &= ~ballot(mine);
-      }
-    }
+    tag_hist_add(hist, tag, v, true);
   }
   if (mism) {
     res->overflow = 1;
@@ -2321,7 +2200,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(16))) void k_fr
       if (c_in - c_own) atomicAdd((unsigned long long*)&dd.st->stats[2], (unsigned long long)(c_in - c_own));
     }
   }
-  if constexpr (LDSH) tag_hist_flush(hist, res->divide);
+  tag_hist_flush(hist, res->divide);
   __syncthreads();  // every wave of the block has read n_rec
   if (threadIdx.x == 0) {
     // every block has read n_rec before its own count here
@@ -2435,7 +2314,7 @@ __global__ __launch_bounds__(256, 3) void k_perft_dfs(const Board* __restrict__ 
       }
     }
     if (__syncthreads_or(valid) == 0) break;  // every lane of the block is done
-    c2c_group<STM_P, CAP>(sh, valid, p, tag, divide, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    c2c_group<STM_P, CAP>(sh, valid, p, tag, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
   }
   tag_hist_flush(sh.hist, divide);
 }
@@ -2572,74 +2451,17 @@ hipError_t launch_wide_slice(hipStream_t st, const Range* lvl, const u64* chunk_
   return hipGetLastError();
 }
 
-hipError_t launch_slice(hipStream_t st, Range* rng, u32 shard, u32 n_shards) {
-  hipLaunchKernelGGL(k_slice, dim3(1), dim3(1), 0, st, rng, shard, n_shards);
-  return hipGetLastError();
-}
-
-#ifdef DC_AB_KNOBS
-// Final-stage selection (for A/B measurement): DC_FINAL=2b forces k_count2b
-// under REF (k_count2c: 24 child slots per parent, the best of 20/24/28).
-static int final_variant() {
-  static const int v = ab_is("DC_FINAL", "2b") ? 0 : 1;
-  return v;
-}
-#endif
-
-template <u32 CAP, int PHASE, bool BULK, int MINW = 4>
-static void launch_count2c_cap(hipStream_t st, int stm, const Board* nodes, const uint16_t* tags, const Range* rng,
-                               u64* divide) {
+static void launch_count2c(hipStream_t st, int stm, const Board* nodes, const uint16_t* tags, const Range* rng,
+                           u64* divide) {
   // divide is the first member of the run's PerftResult (perft_enqueue): its
   // next_chunk field, zeroed with the block at the start of the run, is the
   // chunk counter
   static_assert(offsetof(PerftResult, divide) == 0, "divide heads PerftResult");
   u32* next = &reinterpret_cast<PerftResult*>(divide)->next_chunk;
   with_stm(stm, [&](auto S) {
-    launch_resident(k_count2c<S(), CAP, PHASE, BULK, MINW>, 256, kMaxGrid, st, nodes, tags, rng, divide, next);
+    launch_resident(k_count2c<S(), kC2cCap>, 256, kMaxGrid, st, nodes, tags, rng, divide, next);
   });
 }
-
-static void launch_count2c(hipStream_t st, int stm, const Board* nodes, const uint16_t* tags, const Range* rng,
-                           u64* divide) {
-  // DC_C2C_PHASE (A/B and timing only): 3 = no bulk split; 1, 2 = partial phases
-  static const int phase = (int)ab_int("DC_C2C_PHASE", 0, 10);
-  // DC_C2C_WAVES (A/B): minimum waves per SIMD of the launch bounds, i.e. the
-  // VGPR budget.  4 (default since round 2): 128 VGPRs with 52 B/lane of
-  // spills; 3: 140 VGPRs, no scratch.  perft(7) count2: 0.498-0.505 vs
-  // 0.523-0.532 ms (tools/ab_phase.sh, round 2; round 1's body measured equal).
-  // Two round-2 dead ends: 16 instead of 24 slots per parent (LDS for 4
-  // blocks per CU) measured the same, and a chunk prefetch pipeline (next
-  // chunk's parents in registers across the group, next index fetched a group
-  // ahead) was slower at either budget (0.542 / 0.574 ms).
-  static const int waves = (int)ab_int("DC_C2C_WAVES", 4, 10);
-#ifdef DC_AB_KNOBS
-  if (phase == 1) launch_count2c_cap<kC2cCap, 1, true>(st, stm, nodes, tags, rng, divide);
-  else if (phase == 2) launch_count2c_cap<kC2cCap, 2, true>(st, stm, nodes, tags, rng, divide);
-  else if (phase == 3) launch_count2c_cap<kC2cCap, 0, false>(st, stm, nodes, tags, rng, divide);
-  else if (phase == 5) launch_count2c_cap<kC2cCap, 5, true>(st, stm, nodes, tags, rng, divide);
-  else if (phase == 6) launch_count2c_cap<kC2cCap, 6, true>(st, stm, nodes, tags, rng, divide);
-  else if (phase == 7) launch_count2c_cap<kC2cCap, 7, true>(st, stm, nodes, tags, rng, divide);
-  else if (phase == 8) launch_count2c_cap<kC2cCap, 8, true>(st, stm, nodes, tags, rng, divide);
-  else if (waves == 4) launch_count2c_cap<kC2cCap, 0, true, 4>(st, stm, nodes, tags, rng, divide);
-  else launch_count2c_cap<kC2cCap, 0, true, 3>(st, stm, nodes, tags, rng, divide);
-#else
-  (void)phase;
-  (void)waves;
-  launch_count2c_cap<kC2cCap, 0, true, 4>(st, stm, nodes, tags, rng, divide);
-#endif
-}
-
-#ifdef DC_AB_KNOBS
-// A/B build only: the last PHASE 8 launch's per-block timeline
-// (kTraceWords u64 per block: entry, exit, chunks, counter-wait ticks, XCC id,
-// last counter return, grid size).
-extern "C" __attribute__((visibility("default"))) int dc_ab_c2c_trace(u64* out, u64 n_words) {
-  const u64 n = std::min<u64>(n_words, (u64)kTraceBlocks * kTraceWords);
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_c2c_trace), n * sizeof(u64), 0, hipMemcpyDeviceToHost) == hipSuccess
-             ? 0
-             : -1;
-}
-#endif
 
 #ifdef DC_AB_KNOBS
 extern "C" __attribute__((visibility("default"))) int dc_ab_top_trace(u64* out) {
@@ -2763,26 +2585,11 @@ hipError_t launch_front(hipStream_t st, int stm0, u32 depth, const Board* root, 
 hipError_t launch_front_fold(hipStream_t st, const FrontDedup& dd, const Board* out, const Range* rng_out,
                              PerftResult* res) {
   // (a fixed grid: the record count is on the device; ~200k records at startpos perft(7))
-  u32 grid = kFoldGrid;
-#ifdef DC_AB_KNOBS
-  // DC_FOLD_GRID=N: the grid; DC_FOLD_LDS=0: the form without LDS
-  static const int ab_grid = (int)ab_int("DC_FOLD_GRID", 0, 10);
-  static const bool ab_no_lds = [] {
-    const char* e = ab_env("DC_FOLD_LDS");
-    return e && std::atoi(e) == 0;
-  }();
-  if (ab_grid > 0) grid = (u32)ab_grid;
-  if (ab_no_lds) {
-    hipLaunchKernelGGL(k_front_fold<false>, dim3(grid), dim3(256), 0, st, dd, out, rng_out, res);
-    return hipGetLastError();
-  }
-#endif
-  hipLaunchKernelGGL(k_front_fold<true>, dim3(grid), dim3(256), 0, st, dd, out, rng_out, res);
+  hipLaunchKernelGGL(k_front_fold, dim3(kFoldGrid), dim3(256), 0, st, dd, out, rng_out, res);
   return hipGetLastError();
 }
 
-// Product: REF -> k_count2c (the bulk split), FIDE -> k_count2b<FideRules>.
-// k_count2b<RefRules> (DC_FINAL=2b) is compiled only into the A/B build.
+// REF -> k_count2c (the bulk split), FIDE -> k_count2b<FideRules>.
 hipError_t launch_final(hipStream_t st, u32 rules, int stm, int plies, const Board* nodes, const uint16_t* meta,
                         const uint16_t* tags, const Range* rng, u64 n_bound, u64* divide) {
   // divide is the run's PerftResult.divide (its first member): k_count2b's chunk counter sits in the same block
@@ -2795,20 +2602,13 @@ hipError_t launch_final(hipStream_t st, u32 rules, int stm, int plies, const Boa
     });
     return hipGetLastError();
   }
-  auto count2b = [&](auto R) {
+  if (rules == 0) {
+    launch_count2c(st, stm, nodes, tags, rng, divide);
+  } else {
     with_stm(stm, [&](auto S) {
-      launch_resident(k_count2b<tagged<decltype(R)>, S()>, 256, kMaxGrid, st, nodes, meta, tags, rng, divide,
-                      next_chunk);
+      launch_resident(k_count2b<FideRules, S()>, 256, kMaxGrid, st, nodes, meta, tags, rng, divide, next_chunk);
     });
-  };
-#ifdef DC_AB_KNOBS
-  if (rules == 0 && final_variant() == 0) {
-    count2b(type_tag<RefRules>{});
-    return hipGetLastError();
   }
-#endif
-  if (rules == 0) launch_count2c(st, stm, nodes, tags, rng, divide);
-  else count2b(type_tag<FideRules>{});
   return hipGetLastError();
 }
 

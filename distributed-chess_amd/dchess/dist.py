@@ -7,7 +7,7 @@ front end selects the shard's nodes by index -- k_front for REF depth 6/7 at
 split 3, k_make_count over the top kernel's move words otherwise; strided
 shards carry equal leaf counts to ~1 %, contiguous eighths differed by 1.47x).  The per-root-move divide vectors are summed with
 one all-reduce -- RCCL over xGMI with the "nccl" backend, gloo on CPU in the
-tests.  (The A/B build's DC_SHARD=contig knob takes contiguous slices.)
+tests.  (Contiguous slices were an A/B-build variant, removed once decided.)
 
 Replay.  Game ids [0, n_total) are split into contiguous ranges of whole
 64-game bitmap words (replay_range == dc_replay_shard_range).  Rank r

@@ -28,7 +28,7 @@ REG_GRANULE = 8
 FIELDS = ("vgpr_count", "agpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
 
 # mangled-name fragments
-FOLD = "12k_front_foldILb1E"
+FOLD = "12k_front_foldENS_"  # (no template parameter since its form without LDS was removed)
 COPY = "13k_copy_result"
 FRONT = "7k_frontILi0ELi1ELb1E"
 COUNT = "9k_count3cILi0ELj4592ELi4EjLb1E"

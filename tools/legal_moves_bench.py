@@ -5,16 +5,15 @@ Input: the 615 FIDE test positions (tests/test_gpu_legal_moves.py fide_set)
 tiled to --n positions, uploaded once.  After warm-up it times
 
   - the _device call end to end (a host clock around the call, which returns
-    after a stream synchronise), per emit variant;
+    after a stream synchronise);
   - the "legal_count" and "legal_emit" kernels (dc_ctx_kernel_stats) in a
     separate profiling-on pass;
   - host-form calls of n = 1 and n = 64 positions, in microseconds per call;
   - what a caller needs for the same answer without the list call:
     dc_validate_batch over all 4,096 (from, to) pairs of 4,096 positions.
 
-With the A/B library (make -C distributed-chess_amd ab; DCHESS_LIB=.../libdchess_ab.so)
-the staged and the plain emit alternate in the same run (DC_LEGAL_EMIT); with
-the product library only the shipped emit runs.  Prints one JSON line.
+Prints one JSON line (the figures under variants.shipped: an earlier staged
+emit was timed beside the shipped one).
 """
 import argparse
 import ctypes as C
@@ -45,12 +44,7 @@ def main():
     import test_gpu_legal_moves as T
     base = T.fide_set().pos
     eng = dchess.Engine(0)
-    ab = bool(os.environ.get("DCHESS_LIB"))
-    variants = ["staged", "plain"] if ab else ["shipped"]
-
-    def select(v):
-        if ab:
-            os.environ["DC_LEGAL_EMIT"] = v
+    variants = ["shipped"]
 
     n = a.n
     pos = base[np.arange(n) % len(base)]
@@ -61,26 +55,18 @@ def main():
     d_mv = eng.alloc(2 * max(total, 1))
     out = {"n": n, "moves": total, "lib": os.path.basename(dchess.LIB_PATH), "variants": {}}
 
-    # ---- end to end, variants alternating
+    # ---- end to end
     wall = {v: [] for v in variants}
-    ref_moves = None
     for r in range(a.warmup + a.reps):
         for v in variants:
-            select(v)
             t0 = time.perf_counter()
             eng.legal_moves_device(d_pos, n, d_off, d_st, d_mv, total, FIDE)
             dt = time.perf_counter() - t0
             if r >= a.warmup:
                 wall[v].append(dt)
-            elif r == 0:  # both variants write the same list
-                got = d_mv.download(np.uint16, total)
-                if ref_moves is None:
-                    ref_moves = got
-                assert (got == ref_moves).all(), v
     # ---- kernel times, profiling on
     eng.set_profiling(True)
     for v in variants:
-        select(v)
         eng.reset_stats()
         for _ in range(a.reps):
             eng.legal_moves_device(d_pos, n, d_off, d_st, d_mv, total, FIDE)
@@ -108,7 +94,6 @@ def main():
         args = (eng.ctx, FIDE, dchess._ptr(p), k, dchess._ptr(off), dchess._ptr(st), dchess._ptr(mv), len(mv),
                 C.byref(tot))
         for v in variants:
-            select(v)
             for _ in range(200):
                 assert L.dc_legal_moves_batch(*args) == 0
             t0 = time.perf_counter()

@@ -1,5 +1,6 @@
 """Average k_count2* time of perft(startpos, D) over N runs (HIP events on the
-context stream); no parity check, so it can time the DC_C2C_PHASE variants."""
+context stream), from the kernel statistics of a profiling pass; the count is
+printed, not checked."""
 import os
 import sys
 
