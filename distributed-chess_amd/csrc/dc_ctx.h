@@ -249,6 +249,9 @@ struct dc_ctx {
   // dc_outcome.hip), the block records behind their totals, the host form's outcomes
   DBuf<u64> outcome_hist, outcome_part, outcomes;
   DBuf<uint8_t> san;  // dc_replay_san's host form: ply-major [n_plies][n_games] SAN bytes
+  // dc_san_resolve: the host form's tokens and first_bad; either form's five counters
+  DBuf<u32> san_tokens, san_first_bad;
+  DBuf<u64> san_counts;
   // games adjudicated per launch: 1 GiB of history (dc_test_outcome_chunk_games lowers it)
   u32 outcome_chunk_games = 177664;
   // the state hash's replay pre-pass is skipped past this many bytes of its

@@ -30,6 +30,15 @@ GO_NAMES = ("ongoing", "white_wins", "black_wins", "stalemate", "dead", "fivefol
 # dc_replay_san's byte (DC_SAN_*): bits 0-2 the moved kind (KINDS order), then these flags; 0xFF = no move
 SAN_CAPTURE, SAN_FILE, SAN_RANK, SAN_CHECK, SAN_MATE = 0x08, 0x10, 0x20, 0x40, 0x80
 SAN_NONE = 0xFF
+# notation input: the token word of dc_san_parse / dc_san_resolve (include/dchess.h), the resolver's
+# flagged move words and its counters (DC_SR_*)
+SAN_TOKEN_NONE = 0xFFFFFFFF
+TOK_FILE_GIVEN, TOK_RANK_GIVEN, TOK_OO, TOK_OOO, TOK_X, TOK_CHECK, TOK_MATE = (1 << 12, 1 << 16, 1 << 20, 1 << 21,
+                                                                               1 << 22, 1 << 23, 1 << 24)
+MOVE_NOMATCH, MOVE_AMBIGUOUS, MOVE_MALFORMED = 0x8001, 0x8002, 0x8003
+SR_TOKENS, SR_RESOLVED, SR_NOMATCH, SR_AMBIGUOUS, SR_MALFORMED = range(5)
+SR_COUNT = 5
+PGN_DRAW = 3  # pgn_parse_movetext's result for "1/2-1/2" (0 "*", 1 "1-0", 2 "0-1")
 # dc_perft_stats counters (DC_PS_*), and their names in the published tables' column order
 (PS_NODES, PS_CAPTURES, PS_EP, PS_CASTLES, PS_PROMOTIONS, PS_CHECKS, PS_DISCOVERED, PS_DOUBLE, PS_CHECKMATES,
  PS_STALEMATES, PS_KING_CAPTURES) = range(11)
@@ -121,6 +130,12 @@ def lib():
         "dc_pgn_movetext": (C.c_int, [_vp, _vp, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint8, C.c_uint8, _vp,
                                       C.c_size_t, C.POINTER(C.c_size_t)]),
         "dc_pos_to_fen": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "dc_san_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "dc_pgn_parse_movetext": (C.c_int, [C.c_char_p, C.c_size_t, _vp, C.c_size_t, C.c_uint32,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]),
+        "dc_san_resolve": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+        "dc_san_resolve_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
         "dc_history_append": (C.c_int, [C.c_char_p, _vp, _vp, C.c_uint32, C.c_size_t, _vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
         "dc_gen_games": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -199,6 +214,62 @@ def pgn_movetext(moves, san, result, first_fullmove=1, first_stm=0):
     buf = C.create_string_buffer(n.value + 1)
     _check(lib().dc_pgn_movetext(*args, buf, n.value + 1, C.byref(n)), "dc_pgn_movetext")
     return buf.value.decode()
+
+
+def san_parse(text):
+    """dc_san_parse: one SAN token ('Nbd2', 'exd8=Q+', 'O-O', 'Ng1f3') as its
+    token word; raises DChessError (EINVAL) for anything else."""
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    tok = C.c_uint32()
+    _check(lib().dc_san_parse(raw, len(raw), C.byref(tok)), f"dc_san_parse({text!r})")
+    return int(tok.value)
+
+
+def pgn_parse_movetext(text):
+    """dc_pgn_parse_movetext: one game's movetext -> (tokens uint32 [n], result
+    (0 '*' or none, 1 '1-0', 2 '0-1', PGN_DRAW), first_fullmove, first_stm,
+    consumed bytes of the utf-8 text).  A word that is no SAN token raises
+    DChessError with .offset set to where it begins."""
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    n, res, ff, fs, used = C.c_uint32(), C.c_uint8(), C.c_uint32(), C.c_uint8(), C.c_size_t()
+    outs = (C.byref(n), C.byref(res), C.byref(ff), C.byref(fs), C.byref(used))
+    st = lib().dc_pgn_parse_movetext(raw, len(raw), None, 1, 0, *outs)
+    if st != SUCCESS:
+        e = DChessError(st, f"dc_pgn_parse_movetext (offset {used.value})")
+        e.offset = int(used.value)
+        raise e
+    tokens = np.zeros(n.value, np.uint32)
+    if n.value:
+        _check(lib().dc_pgn_parse_movetext(raw, len(raw), _ptr(tokens), 1, n.value, *outs), "dc_pgn_parse_movetext")
+    return tokens, int(res.value), int(ff.value), int(fs.value), int(used.value)
+
+
+def pgn_games(text):
+    """Splits PGN text into [(tags dict, movetext)].  A line that begins with
+    '[' is a tag line; the first tag line after movetext begins the next game.
+    A '[' at the start of a line inside a comment is therefore not supported.
+    Games without tags that share one movetext block stay together: walk them
+    with pgn_parse_movetext's `consumed`."""
+    import re
+    tag = re.compile(r'\[\s*(\w+)\s+"((?:[^"\\]|\\.)*)"\s*\]')
+    games, tags, body = [], {}, []
+
+    def flush():
+        if tags or any(l.strip() for l in body):
+            games.append((dict(tags), "\n".join(body).strip()))
+
+    for line in text.splitlines():
+        if line.startswith("["):
+            if any(l.strip() for l in body):
+                flush()
+                tags, body = {}, []
+            m = tag.match(line)
+            if m:
+                tags[m.group(1)] = re.sub(r"\\(.)", r"\1", m.group(2))
+        else:
+            body.append(line)
+    flush()
+    return games
 
 
 def exported_symbols():
@@ -583,6 +654,32 @@ class Engine:
                                           _dptr(d_outcomes), _dptr(d_san), _dptr(d_bitmap), _dptr(d_digests),
                                           _ptr(counts), C.byref(st)), "dc_replay_san_device")
         return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def resolve_san(self, tokens, start=None, want_first_bad=True, want_counts=True):
+        """dc_san_resolve (RULES_FIDE): tokens uint32 [n_plies, n_games] ply-major
+        (SAN_TOKEN_NONE = no move) -> (moves uint16 [n_plies, n_games] with
+        MOVE_NOMATCH / MOVE_AMBIGUOUS / MOVE_MALFORMED where no single legal move
+        fits, first_bad uint32 [n_games], counts u64[SR_COUNT])."""
+        tokens = np.ascontiguousarray(tokens, np.uint32)
+        n_plies, n_games = tokens.shape
+        moves = np.zeros((n_plies, n_games), np.uint16)
+        first_bad = np.zeros(n_games, np.uint32) if want_first_bad else None
+        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        _check(lib().dc_san_resolve(self.ctx, _ptr(sp), _ptr(tokens), n_games, n_plies, _ptr(moves),
+                                    _ptr(first_bad), _ptr(counts)), "dc_san_resolve")
+        return moves, first_bad, counts
+
+    def resolve_san_device(self, d_tokens, n_games, n_plies, d_moves, d_first_bad=None, start=None,
+                           want_counts=True):
+        """dc_san_resolve_device on DeviceBuffers or raw device addresses (d_tokens:
+        4 bytes a ply, d_moves: 2, d_first_bad: 4 bytes a game or None).  Returns
+        counts u64[SR_COUNT] (None if not wanted)."""
+        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        _check(lib().dc_san_resolve_device(self.ctx, _ptr(sp), _dptr(d_tokens), n_games, n_plies, _dptr(d_moves),
+                                           _dptr(d_first_bad), _ptr(counts)), "dc_san_resolve_device")
+        return counts
 
     def state_hash(self, moves, names, start=None, history=""):
         """keccak256(serde_json(final GameState)) of every game of a replay batch

@@ -131,7 +131,8 @@ int dc_version(void);
  * "validate", "replay", "gen_games", "expand_count", "expand_write", "count1", "count2",
  * "legal_count" (units: positions), "legal_emit" (units: moves); beside them
  * "legal_scan", "legal_fixup" and, for batches of at most 256, "legal_small";
- * "replay_outcome" and "replay_san" (units: moves consumed). */
+ * "replay_outcome" and "replay_san" (units: moves consumed);
+ * "san_resolve" (units: tokens other than DC_SAN_TOKEN_NONE). */
 int dc_ctx_set_profiling(dc_ctx* ctx, int enable);
 int dc_ctx_kernel_stats(dc_ctx* ctx, const char* kernel, dc_kernel_stats* out);
 int dc_ctx_reset_stats(dc_ctx* ctx);
@@ -385,6 +386,96 @@ int dc_pgn_movetext(const uint16_t* moves, const uint8_t* san, uint32_t n_plies,
  * kind OTHER; DC_EINVAL for stm > 1 or ep outside -1..63. */
 int dc_pos_to_fen(const dc_pos* pos, uint32_t halfmove, uint32_t fullmove, char* out, size_t out_cap,
                   size_t* out_len);
+
+/* ---------------------------------------------------------- notation input
+ * The way back: SAN / PGN movetext -> move words.  A host parser turns text
+ * into one token word per written move; dc_san_resolve finds, per position and
+ * on the device, the one legal move a token means (DC_RULES_FIDE only).
+ *
+ * Token word (uint32, ply-major [n_plies][n_games] like the moves):
+ *   bits 0-5    target square (8*x+y)
+ *   bits 6-8    piece kind, cell kind 0 P .. 5 K
+ *   bits 9-11   promotion 0 none, 1 N, 2 B, 3 R, 4 Q
+ *   bit  12     origin file given       bits 13-15  origin file
+ *   bit  16     origin rank given       bits 17-19  origin rank
+ *   bit  20     O-O                     bit  21     O-O-O
+ *               (with either castle bit, bits 0-19 are 0)
+ *   bit  22     "x" written   bit 23  "+" written   bit 24  "#" written
+ *   bits 25-31  0
+ * Bits 22-24 are recorded by the parser and ignored by the resolver.
+ * DC_SAN_TOKEN_NONE means "no move": skipped, the turn does not flip
+ * (DC_MOVE_NONE's meaning). */
+#define DC_SAN_TOKEN_NONE (0xFFFFFFFFu)
+#define DC_PGN_DRAW 3 /* dc_pgn_parse_movetext's result for "1/2-1/2" */
+/* One SAN token, on the host (no context):
+ *   [KQRBN]? [a-h]? [1-8]? x? [a-h][1-8] (=[QRBN])? [+#]? [!?]*
+ * or O-O / O-O-O (letter O or digit 0) with the same suffixes.  No piece
+ * letter means a pawn; letters are case-sensitive ("bxc3" is a pawn, "Bxc3" a
+ * bishop).  Everything dc_san_format writes parses, and so do the long forms
+ * ("Ng1f3", "e2e4").  Anything else is DC_EINVAL: an empty string, "e.p.", a
+ * promotion on a piece letter, trailing characters. */
+int dc_san_parse(const char* text, size_t len, uint32_t* token);
+/* One game's movetext, on the host: the token of written move k goes to
+ * tokens[k * stride] (stride 0 counts as 1).  Skipped: move numbers ("12.",
+ * "12..."), {...} comments, ";" comments to the end of the line, "$n" NAGs and
+ * nested "( ... )" variations.  Reading stops after the first result token:
+ * *result is 0 for "*" or the end of the text, 1 for "1-0", 2 for "0-1" (the
+ * DC_GO_* codes) and DC_PGN_DRAW for "1/2-1/2".  *first_fullmove / *first_stm
+ * come from the first move number seen before any move ("N..." means Black;
+ * defaults 1 and 0).  *consumed is the number of bytes read through the result
+ * token, so a caller can walk a stream of games.  Sizing as dc_pgn_movetext's:
+ * with tokens NULL or cap 0 only *n_tokens and the other outputs are written;
+ * with 0 < cap < *n_tokens the call is DC_EINVAL, *n_tokens set and nothing
+ * written past cap.  A word that is neither skippable nor a SAN token is
+ * DC_EINVAL with *consumed the offset of that word.  n_tokens is required, the
+ * other outputs may be NULL.  Tag pairs ("[Event ...]") are not read here. */
+int dc_pgn_parse_movetext(const char* text, size_t len, uint32_t* tokens, size_t stride, uint32_t cap,
+                          uint32_t* n_tokens, uint8_t* result, uint32_t* first_fullmove, uint8_t* first_stm,
+                          size_t* consumed);
+
+/* dc_san_resolve: tokens -> move words, one game per lane, from start (NULL:
+ * the start position).  Per ply: DC_SAN_TOKEN_NONE gives DC_MOVE_NONE and
+ * changes nothing.  Otherwise the side to move's pieces that fit the token and
+ * may LEGALLY move to its target are counted (pins, checks and en-passant
+ * legality decide, never geometry alone):
+ *   piece tokens (N B R Q K)  own pieces of the kind, on the origin file / rank
+ *                             if given; a K token never means a castle
+ *   castle tokens             the king, two files towards h (O-O) or a (O-O-O)
+ *   pawn tokens               own pawns on the origin file, or on the TARGET's
+ *                             file if none is given ("e4" is the push even when
+ *                             "dxe4" is legal; "exd6" a capture, en passant
+ *                             included), on the origin rank if given; the promo
+ *                             field must be 1..4 exactly when the target is on
+ *                             the last rank, else the token has no match
+ * Exactly one: its move word (promo field included) is written, the move made
+ * and the turn flipped.  Otherwise one of the flagged words below is written,
+ * the position stays, and the next token is tried against it.  The flagged
+ * words have bit 15 set, which dc_replay* counts as validated and rejected: a
+ * resolved array can go to dc_replay_outcome / dc_replay_san as it is.
+ * first_bad[g] (optional) is the first ply of game g with a flagged word, or
+ * n_plies; counts (optional, host) has DC_SR_COUNT entries summed over the batch.
+ * The resolver does not adjudicate and keeps neither history nor clocks: after
+ * mate or stalemate every token is DC_MOVE_NOMATCH by itself (no legal move),
+ * but after a fivefold, 75-move or dead-position ending it goes on resolving;
+ * dc_replay_outcome on the resolved moves cuts the game at end_ply.
+ * n_games == 0 or n_plies == 0 is a successful no-op (first_bad all 0).
+ * DC_EINVAL: start->stm > 1, or NULL tokens / moves with n_games && n_plies.
+ * Kernel timing name: "san_resolve" (units: tokens other than NONE).
+ * The _device form takes d_tokens, d_moves and d_first_bad in device memory. */
+#define DC_MOVE_NOMATCH   0x8001u /* no legal move fits the token */
+#define DC_MOVE_AMBIGUOUS 0x8002u /* two or more legal moves fit */
+#define DC_MOVE_MALFORMED 0x8003u /* kind > 5, promo > 4, reserved bits, both castle bits, castle with other
+                                     fields, promo on a piece */
+#define DC_SR_TOKENS    0 /* tokens other than DC_SAN_TOKEN_NONE */
+#define DC_SR_RESOLVED  1
+#define DC_SR_NOMATCH   2
+#define DC_SR_AMBIGUOUS 3
+#define DC_SR_MALFORMED 4
+#define DC_SR_COUNT     5
+int dc_san_resolve(dc_ctx* ctx, const dc_pos* start, const uint32_t* tokens, uint32_t n_games, uint32_t n_plies,
+                   uint16_t* moves, uint32_t* first_bad, uint64_t* counts);
+int dc_san_resolve_device(dc_ctx* ctx, const dc_pos* start, const uint32_t* d_tokens, uint32_t n_games,
+                          uint32_t n_plies, uint16_t* d_moves, uint32_t* d_first_bad, uint64_t* counts);
 
 /* Seeded synthetic games: rng = splitmix64 from seed ^ game_id;
  * per ply one draw r: (r & 0xFF) < noise_per_256 -> move (r>>8)&0xFFF, else the

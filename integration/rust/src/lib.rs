@@ -89,6 +89,17 @@ pub mod sys {
     pub const DC_SAN_RANK: u8 = 0x20;
     pub const DC_SAN_CHECK: u8 = 0x40;
     pub const DC_SAN_MATE: u8 = 0x80;
+    pub const DC_SAN_TOKEN_NONE: u32 = 0xFFFF_FFFF;
+    pub const DC_PGN_DRAW: u8 = 3;
+    pub const DC_MOVE_NOMATCH: u16 = 0x8001;
+    pub const DC_MOVE_AMBIGUOUS: u16 = 0x8002;
+    pub const DC_MOVE_MALFORMED: u16 = 0x8003;
+    pub const DC_SR_TOKENS: usize = 0;
+    pub const DC_SR_RESOLVED: usize = 1;
+    pub const DC_SR_NOMATCH: usize = 2;
+    pub const DC_SR_AMBIGUOUS: usize = 3;
+    pub const DC_SR_MALFORMED: usize = 4;
+    pub const DC_SR_COUNT: usize = 5;
     pub const DC_PS_NODES: usize = 0;
     pub const DC_PS_CAPTURES: usize = 1;
     pub const DC_PS_EP: usize = 2;
@@ -172,6 +183,16 @@ pub mod sys {
                                out_len: *mut usize) -> c_int;
         pub fn dc_pos_to_fen(pos: *const dc_pos, halfmove: u32, fullmove: u32, out: *mut c_char, out_cap: usize,
                              out_len: *mut usize) -> c_int;
+        // notation input
+        pub fn dc_san_parse(text: *const c_char, len: usize, token: *mut u32) -> c_int;
+        pub fn dc_pgn_parse_movetext(text: *const c_char, len: usize, tokens: *mut u32, stride: usize, cap: u32,
+                                     n_tokens: *mut u32, result: *mut u8, first_fullmove: *mut u32,
+                                     first_stm: *mut u8, consumed: *mut usize) -> c_int;
+        pub fn dc_san_resolve(ctx: *mut dc_ctx, start: *const dc_pos, tokens: *const u32, n_games: u32,
+                              n_plies: u32, moves: *mut u16, first_bad: *mut u32, counts: *mut u64) -> c_int;
+        pub fn dc_san_resolve_device(ctx: *mut dc_ctx, start: *const dc_pos, d_tokens: *const u32, n_games: u32,
+                                     n_plies: u32, d_moves: *mut u16, d_first_bad: *mut u32,
+                                     counts: *mut u64) -> c_int;
         pub fn dc_replay_info(ctx: *mut dc_ctx, rules: u32, start: *const dc_pos, moves: *const u16, n_games: u32,
                               n_plies: u32, bitmap: *mut u64, digests: *mut u64, info: *mut u8,
                               stats: *mut dc_replay_stats) -> c_int;
@@ -419,6 +440,23 @@ impl Engine {
         Ok((out, text))
     }
 
+    /// One game's SAN tokens (parse_movetext's) as move words (dc_san_resolve,
+    /// n_games = 1): (moves, the first ply with a flagged word or the number of
+    /// plies, the DC_SR_* counters).  A token no single legal move fits gives
+    /// DC_MOVE_NOMATCH / _AMBIGUOUS / _MALFORMED there and leaves the position.
+    pub fn resolve_san(&self, start: Option<&sys::dc_pos>, tokens: &[u32])
+                       -> Result<(Vec<u16>, u32, [u64; sys::DC_SR_COUNT]), DcError> {
+        let n_plies = u32::try_from(tokens.len()).map_err(|_| DcError {
+            status: sys::DC_EINVAL, what: "dc_san_resolve", text: "more than u32::MAX tokens".into() })?;
+        let mut moves = vec![sys::DC_MOVE_NONE; tokens.len()];
+        let mut first_bad = 0u32;
+        let mut counts = [0u64; sys::DC_SR_COUNT];
+        let sp = start.map_or(std::ptr::null(), |p| p as *const sys::dc_pos);
+        check(unsafe { sys::dc_san_resolve(self.0, sp, tokens.as_ptr(), 1, n_plies, moves.as_mut_ptr(),
+                                           &mut first_bad, counts.as_mut_ptr()) }, "dc_san_resolve")?;
+        Ok((moves, first_bad, counts))
+    }
+
     /// The published perft tables' columns for one position (dc_perft_stats_shard;
     /// split_depth 1, shard 0 of 1 is the whole tree).  Returns (totals, one row
     /// of DC_PS_COUNT counters per root move, the root moves).
@@ -497,6 +535,46 @@ pub fn pgn_movetext(moves: &[u16], san: &[u8], first_fullmove: u32, first_stm: u
     check(unsafe { sys::dc_pgn_movetext(moves.as_ptr(), san.as_ptr(), n_plies, 1, first_fullmove, first_stm, result,
                                         out.as_mut_ptr() as *mut c_char, out.len(), &mut len) }, "dc_pgn_movetext")?;
     text_of(out, len, "pgn_movetext")
+}
+
+/// One SAN token ("Nbd2", "exd8=Q+", "O-O") as its token word (dc_san_parse, host only).
+pub fn san_parse(text: &str) -> Result<u32, DcError> {
+    let mut token = 0u32;
+    check(unsafe { sys::dc_san_parse(text.as_ptr() as *const c_char, text.len(), &mut token) }, "dc_san_parse")?;
+    Ok(token)
+}
+
+/// One game's movetext read by dc_pgn_parse_movetext (host only).
+#[derive(Clone, Debug, Default, PartialEq, Eq)]
+pub struct Movetext {
+    pub tokens: Vec<u32>,
+    /// 0 "*" or none, 1 "1-0", 2 "0-1", DC_PGN_DRAW "1/2-1/2"
+    pub result: u8,
+    pub first_fullmove: u32,
+    pub first_stm: u8,
+    /// bytes read through the result token: the next game begins there
+    pub consumed: usize,
+}
+
+/// Parses one game's movetext; on a word that is no SAN token the error's text
+/// names the byte offset of that word.
+pub fn parse_movetext(text: &str) -> Result<Movetext, DcError> {
+    let p = text.as_ptr() as *const c_char;
+    let mut m = Movetext::default();
+    let mut n = 0u32;
+    let st = unsafe { sys::dc_pgn_parse_movetext(p, text.len(), std::ptr::null_mut(), 1, 0, &mut n, &mut m.result,
+                                                 &mut m.first_fullmove, &mut m.first_stm, &mut m.consumed) };
+    if st != sys::DC_SUCCESS {
+        return Err(DcError { status: st, what: "dc_pgn_parse_movetext",
+                             text: format!("no SAN token at byte {}", m.consumed) });
+    }
+    m.tokens = vec![sys::DC_SAN_TOKEN_NONE; n as usize];
+    if n > 0 {
+        check(unsafe { sys::dc_pgn_parse_movetext(p, text.len(), m.tokens.as_mut_ptr(), 1, n, &mut n, &mut m.result,
+                                                  &mut m.first_fullmove, &mut m.first_stm, &mut m.consumed) },
+              "dc_pgn_parse_movetext")?;
+    }
+    Ok(m)
 }
 
 /// The FEN of a position (dc_pos_to_fen, host only).
