@@ -19,7 +19,7 @@ std::atomic<uint64_t> dcapi::g_alloc_epoch{0};
 // ================================================================ context
 extern "C" {
 
-int dc_version(void) { return 100; }
+int dc_version(void) { return 101; }  // 101: the *_starts calls
 
 const char* dc_strerror(int s) {
   switch (s) {

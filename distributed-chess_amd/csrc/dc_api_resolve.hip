@@ -7,21 +7,27 @@
 namespace {
 
 // The kernel, its five counters and the unit count; n_games && n_plies.
+// per_game: k_starts_san_resolve with d_starts and d_finals (either may be
+// null) instead, which ignores s.
 int resolve_impl(dc_ctx* c, const dc_pos& s, const uint32_t* d_tokens, uint32_t n_games, uint32_t n_plies,
-                 uint16_t* d_moves, uint32_t* d_first_bad, uint64_t* counts) {
+                 uint16_t* d_moves, uint32_t* d_first_bad, uint64_t* counts, bool per_game = false,
+                 const DevPos* d_starts = nullptr, DevPos* d_finals = nullptr) {
+  const char* name = per_game ? "san_resolve_starts" : "san_resolve";
   u64 h[dc::kResolveCounts] = {};
   HIP_TRY(c->san_counts.ensure(dc::kResolveCounts));
   HIP_TRY(hipMemsetAsync(c->san_counts.p, 0, sizeof h, c->stream));
-  HIP_TRY(c->timed("san_resolve", 0, [&] {
-    return dc::launch_san_resolve(c->stream, reinterpret_cast<const DevPos&>(s), d_tokens, n_games, n_plies, d_moves,
-                                  d_first_bad, c->san_counts.p);
+  HIP_TRY(c->timed(name, 0, [&] {
+    return per_game ? dc::launch_san_resolve_starts(c->stream, d_starts, d_finals, d_tokens, n_games, n_plies, d_moves,
+                                                    d_first_bad, c->san_counts.p)
+                    : dc::launch_san_resolve(c->stream, reinterpret_cast<const DevPos&>(s), d_tokens, n_games, n_plies,
+                                             d_moves, d_first_bad, c->san_counts.p);
   }));
   HIP_TRY(hipMemcpyAsync(h, c->san_counts.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
   const int r = sync_ctx(c);
   if (r != DC_SUCCESS) return r;
   if (counts) std::memcpy(counts, h, sizeof h);
   // the unit count: tokens other than NONE
-  if (c->profiling) c->stats["san_resolve"].units += h[DC_SR_TOKENS];
+  if (c->profiling) c->stats[name].units += h[DC_SR_TOKENS];
   return DC_SUCCESS;
 }
 
@@ -74,6 +80,51 @@ int dc_san_resolve(dc_ctx* c, const dc_pos* start, const uint32_t* tokens, uint3
   if (first_bad)
     HIP_TRY(hipMemcpyAsync(first_bad, c->san_first_bad.p, (size_t)n_games * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            c->stream));
+  return sync_ctx(c);
+}
+
+// ---- the per-game-start forms.  With no plies the kernel still runs: it writes
+// first_bad = 0 and copies the starts to the finals.
+int dc_san_resolve_starts_device(dc_ctx* c, const dc_pos* d_starts, const uint32_t* d_tokens, uint32_t n_games,
+                                 uint32_t n_plies, uint16_t* d_moves, uint32_t* d_first_bad, uint64_t* counts,
+                                 dc_pos* d_finals) {
+  ENTER_WORK(c);
+  if (n_games && n_plies && (!d_tokens || !d_moves)) return DC_EINVAL;
+  if (counts) std::memset(counts, 0, DC_SR_COUNT * sizeof(uint64_t));
+  if (n_games == 0) return DC_SUCCESS;
+  return resolve_impl(c, dc_pos{}, d_tokens, n_games, n_plies, d_moves, d_first_bad, counts, true,
+                      reinterpret_cast<const DevPos*>(d_starts), reinterpret_cast<DevPos*>(d_finals));
+}
+
+int dc_san_resolve_starts(dc_ctx* c, const dc_pos* starts, const uint32_t* tokens, uint32_t n_games, uint32_t n_plies,
+                          uint16_t* moves, uint32_t* first_bad, uint64_t* counts, dc_pos* finals) {
+  ENTER_WORK(c);
+  if (n_games && n_plies && (!tokens || !moves)) return DC_EINVAL;
+  if (starts)
+    for (uint32_t g = 0; g < n_games; ++g)
+      if (starts[g].stm > 1) return DC_EINVAL;
+  if (counts) std::memset(counts, 0, DC_SR_COUNT * sizeof(uint64_t));
+  if (n_games == 0) return DC_SUCCESS;
+  const size_t nm = (size_t)n_games * n_plies;
+  HIP_TRY(c->san_tokens.ensure(std::max<size_t>(nm, 1)));
+  HIP_TRY(c->moves.ensure(std::max<size_t>(nm, 1)));
+  if (first_bad) HIP_TRY(c->san_first_bad.ensure(n_games));
+  if (starts) {
+    HIP_TRY(c->pos.ensure(n_games));
+    HIP_TRY(hipMemcpyAsync(c->pos.p, starts, (size_t)n_games * sizeof(dc_pos), hipMemcpyHostToDevice, c->stream));
+  }
+  if (finals) HIP_TRY(c->finals.ensure(n_games));
+  if (nm) HIP_TRY(hipMemcpyAsync(c->san_tokens.p, tokens, nm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  const int r = resolve_impl(c, dc_pos{}, c->san_tokens.p, n_games, n_plies, c->moves.p,
+                             first_bad ? c->san_first_bad.p : nullptr, counts, true, starts ? c->pos.p : nullptr,
+                             finals ? c->finals.p : nullptr);
+  if (r != DC_SUCCESS) return r;
+  if (nm) HIP_TRY(hipMemcpyAsync(moves, c->moves.p, nm * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  if (first_bad)
+    HIP_TRY(hipMemcpyAsync(first_bad, c->san_first_bad.p, (size_t)n_games * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           c->stream));
+  if (finals)
+    HIP_TRY(hipMemcpyAsync(finals, c->finals.p, (size_t)n_games * sizeof(dc_pos), hipMemcpyDeviceToHost, c->stream));
   return sync_ctx(c);
 }
 

@@ -19,6 +19,27 @@ __device__ __forceinline__ void store_board(Board* p, size_t i, const Board& b) 
   q[1] = ulonglong2{b.b2, b.b3};
 }
 
+// A game's own dc_pos (the *_starts kernels), one strided 40-byte access a game.
+// Read as every FIDE kernel reads one: stm & 1, castle and ep through pack_meta.
+__device__ __forceinline__ void load_start(const DevPos* p, size_t g, Board& b, u32& stm, u32& meta) {
+  const u64* q = reinterpret_cast<const u64*>(p + g);
+  b = Board{q[0], q[1], q[2], q[3]};
+  const u64 w = q[4];  // stm | castle << 8 | (u8)ep << 16 | reserved
+  stm = (u32)w & 1u;
+  meta = pack_meta((uint8_t)(w >> 8), (int8_t)(w >> 16));
+}
+// Written as k_apply_fide leaves one: castle = the rights, ep = the square or -1,
+// the reserved fields 0.
+__device__ __forceinline__ void store_final(DevPos* p, size_t g, const Board& b, u32 stm, u32 meta) {
+  u64* q = reinterpret_cast<u64*>(p + g);
+  q[0] = b.b0;
+  q[1] = b.b1;
+  q[2] = b.b2;
+  q[3] = b.b3;
+  const u32 ep = (meta & META_EP_VALID) ? ((meta >> 4) & 63u) : 0xFFu;
+  q[4] = (u64)(stm | ((meta & 15u) << 8) | (ep << 16));
+}
+
 // Wave-scope ordering of LDS traffic between lanes of one wave.
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -252,6 +252,9 @@ struct dc_ctx {
   // dc_san_resolve: the host form's tokens and first_bad; either form's five counters
   DBuf<u32> san_tokens, san_first_bad;
   DBuf<u64> san_counts;
+  // the *_starts host forms: the per-game clocks and final positions staged (the starts go through pos)
+  DBuf<uint16_t> start_clocks;
+  DBuf<DevPos> finals;
   // games adjudicated per launch: 1 GiB of history (dc_test_outcome_chunk_games lowers it)
   u32 outcome_chunk_games = 177664;
   // the state hash's replay pre-pass is skipped past this many bytes of its

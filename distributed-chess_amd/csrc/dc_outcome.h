@@ -29,6 +29,19 @@ hipError_t launch_replay_outcome(hipStream_t st, const DevPos& start, u32 start_
 hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
                              u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
                              u64* outcomes, uint8_t* san, u64* bitmap, u64* digests, u64* partial);
+// The per-game-start forms (k_starts_replay_outcome, k_starts_replay_san): game g
+// starts from starts[g] with clock min(start_halfmoves[g], 150) (null: the start
+// position, clock 0) and leaves the position it stopped in in finals[g] (null:
+// not wanted).  All three are indexed by the game, whatever `first` is.  The
+// rest as above.
+hipError_t launch_replay_outcome_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
+                                        DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
+                                        u32 count, u64* history, u32 hist_stride, u64* outcomes, u64* bitmap,
+                                        u64* digests, u64* partial);
+hipError_t launch_replay_san_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
+                                    DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
+                                    u32 count, u64* history, u32 hist_stride, u64* outcomes, uint8_t* san, u64* bitmap,
+                                    u64* digests, u64* partial);
 // totals[kOutcomeRecord] =the n_blocks block records combined (xor for the digest xor).
 hipError_t launch_outcome_reduce(hipStream_t st, const u64* partial, u32 n_blocks, u64* totals);
 

@@ -3,6 +3,9 @@
 //   k_replay_outcome   k_replay_fide's replay that also says where each game
 //                      ended and how: checkmate, stalemate, dead position,
 //                      fivefold repetition (FIDE 9.6.1), 75 moves (9.6.2)
+//   k_starts_replay_outcome   the same loop (replay_outcome_lane<true>) with a start
+//                      position and a clock per game, read once before ply 0,
+//                      and the position each game stopped in written once after it
 //   k_outcome_reduce   one workgroup: the block records -> replay counters and
 //                      the result histogram
 //
@@ -37,19 +40,31 @@ __device__ __forceinline__ const u64* key_at(const u64* hist, u32 slot, u32 stri
 
 }  // namespace
 
-__global__ __launch_bounds__(kOutcomeBlock) void k_replay_outcome(Board start, u32 stm0, u32 meta0, u32 clock0,
-                                                                  const uint16_t* __restrict__ moves, u32 n_games,
-                                                                  u32 n_plies, u32 first, u32 count, u64* hist,
-                                                                  u32 stride, u64* __restrict__ outcomes,
-                                                                  u64* __restrict__ bitmap, u64* __restrict__ digests,
-                                                                  u64* __restrict__ partial) {
+// The adjudicating replay of one lane.  STARTS: the game's own start position
+// and clock (starts / clocks, either may be null: the shared start, the shared
+// clock) and, after the loop, the position it stopped in (finals, may be null);
+// all three indexed by the game, not by the chunk's lane.  Otherwise the shared
+// start alone, and the three pointers are not looked at.
+template <bool STARTS>
+__device__ __forceinline__ void replay_outcome_lane(Board start, u32 stm0, u32 meta0, u32 clock0,
+                                                    const DevPos* __restrict__ starts,
+                                                    const uint16_t* __restrict__ clocks, DevPos* __restrict__ finals,
+                                                    const uint16_t* __restrict__ moves, u32 n_games, u32 n_plies,
+                                                    u32 first, u32 count, u64* hist, u32 stride,
+                                                    u64* __restrict__ outcomes, u64* __restrict__ bitmap,
+                                                    u64* __restrict__ digests, u64* __restrict__ partial) {
   const u32 local = blockIdx.x * kOutcomeBlock + threadIdx.x;  // the lane's column of the history
   const u32 g = first + local;
   const bool active = local < count;
   const u32 words = (n_games + 63) >> 6;
   Board b = start;
   u32 stm = stm0, meta = meta0;
-  u32 clock = clock0, base = clock0;  // half-move clock; the clock this run of reversible moves began with
+  u32 clock = clock0;  // half-move clock
+  if (STARTS && active) {
+    if (starts) load_start(starts, g, b, stm, meta);
+    if (clocks) clock = min((u32)clocks[g], kClockEnd);  // the history has slots 0..150
+  }
+  u32 base = clock;  // the clock this run of reversible moves began with
   u32 result = GO_ONGOING, repeats = 1, consumed = 0, end_ply = n_plies;
   u32 validated = 0, accepted = 0;
   bool fresh = active;  // the position has not been adjudicated yet
@@ -123,6 +138,7 @@ __global__ __launch_bounds__(kOutcomeBlock) void k_replay_outcome(Board start, u
     d = board_digest(b, stm);
     if (digests) digests[g] = d;
     outcomes[g] = (u64)result | ((u64)min(repeats, 255u) << 8) | ((u64)(clock & 0xFFFFu) << 16) | ((u64)end_ply << 32);
+    if (STARTS && finals) store_final(finals, g, b, stm, meta);
   }
   // the block's record
   __shared__ u64 ws[kOutcomeBlock / 64][kOutcomeRecord];
@@ -150,6 +166,25 @@ __global__ __launch_bounds__(kOutcomeBlock) void k_replay_outcome(Board start, u
     for (u32 q = 1; q < kOutcomeBlock / 64; ++q) v = (k == 4) ? (v ^ ws[q][k]) : (v + ws[q][k]);
     partial[((size_t)(first / kOutcomeBlock) + blockIdx.x) * kOutcomeRecord + k] = v;
   }
+}
+
+__global__ __launch_bounds__(kOutcomeBlock) void k_replay_outcome(Board start, u32 stm0, u32 meta0, u32 clock0,
+                                                                  const uint16_t* __restrict__ moves, u32 n_games,
+                                                                  u32 n_plies, u32 first, u32 count, u64* hist,
+                                                                  u32 stride, u64* __restrict__ outcomes,
+                                                                  u64* __restrict__ bitmap, u64* __restrict__ digests,
+                                                                  u64* __restrict__ partial) {
+  replay_outcome_lane<false>(start, stm0, meta0, clock0, nullptr, nullptr, nullptr, moves, n_games, n_plies, first,
+                             count, hist, stride, outcomes, bitmap, digests, partial);
+}
+
+__global__ __launch_bounds__(kOutcomeBlock) void k_starts_replay_outcome(
+    Board start, u32 stm0, u32 meta0, const DevPos* __restrict__ starts, const uint16_t* __restrict__ clocks,
+    DevPos* __restrict__ finals, const uint16_t* __restrict__ moves, u32 n_games, u32 n_plies, u32 first, u32 count,
+    u64* hist, u32 stride, u64* __restrict__ outcomes, u64* __restrict__ bitmap, u64* __restrict__ digests,
+    u64* __restrict__ partial) {
+  replay_outcome_lane<true>(start, stm0, meta0, 0, starts, clocks, finals, moves, n_games, n_plies, first, count, hist,
+                            stride, outcomes, bitmap, digests, partial);
 }
 
 __global__ __launch_bounds__(256) void k_outcome_reduce(const u64* __restrict__ partial, u32 n_blocks,
@@ -188,6 +223,20 @@ hipError_t launch_replay_outcome(hipStream_t st, const DevPos& start, u32 start_
   hipLaunchKernelGGL(k_replay_outcome, dim3(blocks_for(count, kOutcomeBlock)), dim3(kOutcomeBlock), 0, st, b,
                      (u32)(start.stm & 1), (u32)pack_meta(start.castle, start.ep), start_halfmove, moves, n_games,
                      n_plies, first, count, history, hist_stride, outcomes, bitmap, digests, partial);
+  return hipGetLastError();
+}
+
+hipError_t launch_replay_outcome_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
+                                        DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
+                                        u32 count, u64* history, u32 hist_stride, u64* outcomes, u64* bitmap,
+                                        u64* digests, u64* partial) {
+  if (count == 0) return hipSuccess;
+  if (first % kOutcomeBlock != 0 || count > hist_stride || (u64)first + count > n_games) return hipErrorInvalidValue;
+  Board b;
+  startpos_board(b);
+  hipLaunchKernelGGL(k_starts_replay_outcome, dim3(blocks_for(count, kOutcomeBlock)), dim3(kOutcomeBlock), 0, st, b,
+                     0u, (u32)pack_meta(15, -1), starts, start_halfmoves, finals, moves, n_games, n_plies, first,
+                     count, history, hist_stride, outcomes, bitmap, digests, partial);
   return hipGetLastError();
 }
 

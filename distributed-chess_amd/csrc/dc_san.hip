@@ -5,6 +5,8 @@
 //                  chunking and the block records are k_replay_outcome's (its
 //                  loop is repeated here so that kernel's code stays as it is;
 //                  k_outcome_reduce combines the records of either)
+//   k_starts_replay_san   the same lane body (replay_san_lane<true>) with
+//                  k_starts_replay_outcome's per-game starts, clocks and finals
 //
 // The byte of ply p has two halves.  Kind, capture and the disambiguation
 // flags are known when the move is validated: the validation's own analysis
@@ -85,21 +87,28 @@ __device__ __forceinline__ bool san_verdict(const Board& b, u32 stm, u32 meta, u
   return stm ? san_verdict_stm<1>(b, meta, m, low) : san_verdict_stm<0>(b, meta, m, low);
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(kOutcomeBlock) void k_replay_san(Board start, u32 stm0, u32 meta0, u32 clock0,
-                                                              const uint16_t* __restrict__ moves, u32 n_games,
-                                                              u32 n_plies, u32 first, u32 count, u64* hist, u32 stride,
-                                                              u64* __restrict__ outcomes, uint8_t* __restrict__ san,
-                                                              u64* __restrict__ bitmap, u64* __restrict__ digests,
-                                                              u64* __restrict__ partial) {
+// One lane's replay; STARTS, starts, clocks and finals as replay_outcome_lane's
+// (dc_outcome.hip).
+template <bool STARTS>
+__device__ __forceinline__ void replay_san_lane(Board start, u32 stm0, u32 meta0, u32 clock0,
+                                                const DevPos* __restrict__ starts, const uint16_t* __restrict__ clocks,
+                                                DevPos* __restrict__ finals, const uint16_t* __restrict__ moves,
+                                                u32 n_games, u32 n_plies, u32 first, u32 count, u64* hist, u32 stride,
+                                                u64* __restrict__ outcomes, uint8_t* __restrict__ san,
+                                                u64* __restrict__ bitmap, u64* __restrict__ digests,
+                                                u64* __restrict__ partial) {
   const u32 local = blockIdx.x * kOutcomeBlock + threadIdx.x;  // the lane's column of the history
   const u32 g = first + local;
   const bool active = local < count;
   const u32 words = (n_games + 63) >> 6;
   Board b = start;
   u32 stm = stm0, meta = meta0;
-  u32 clock = clock0, base = clock0;  // half-move clock; the clock this run of reversible moves began with
+  u32 clock = clock0;  // half-move clock
+  if (STARTS && active) {
+    if (starts) load_start(starts, g, b, stm, meta);
+    if (clocks) clock = min((u32)clocks[g], kClockEnd);  // the history has slots 0..150
+  }
+  u32 base = clock;  // the clock this run of reversible moves began with
   u32 result = GO_ONGOING, repeats = 1, consumed = 0, end_ply = n_plies;
   u32 validated = 0, accepted = 0;
   u32 low = 0;          // kind | capture | file | rank of the last accepted move (ply consumed - 1)
@@ -181,6 +190,7 @@ __global__ __launch_bounds__(kOutcomeBlock) void k_replay_san(Board start, u32 s
     d = board_digest(b, stm);
     if (digests) digests[g] = d;
     outcomes[g] = (u64)result | ((u64)min(repeats, 255u) << 8) | ((u64)(clock & 0xFFFFu) << 16) | ((u64)end_ply << 32);
+    if (STARTS && finals) store_final(finals, g, b, stm, meta);
   }
   // the block's record (k_replay_outcome's)
   __shared__ u64 ws[kOutcomeBlock / 64][kOutcomeRecord];
@@ -208,6 +218,42 @@ __global__ __launch_bounds__(kOutcomeBlock) void k_replay_san(Board start, u32 s
     for (u32 q = 1; q < kOutcomeBlock / 64; ++q) v = (k == 4) ? (v ^ ws[q][k]) : (v + ws[q][k]);
     partial[((size_t)(first / kOutcomeBlock) + blockIdx.x) * kOutcomeRecord + k] = v;
   }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kOutcomeBlock) void k_replay_san(Board start, u32 stm0, u32 meta0, u32 clock0,
+                                                              const uint16_t* __restrict__ moves, u32 n_games,
+                                                              u32 n_plies, u32 first, u32 count, u64* hist, u32 stride,
+                                                              u64* __restrict__ outcomes, uint8_t* __restrict__ san,
+                                                              u64* __restrict__ bitmap, u64* __restrict__ digests,
+                                                              u64* __restrict__ partial) {
+  replay_san_lane<false>(start, stm0, meta0, clock0, nullptr, nullptr, nullptr, moves, n_games, n_plies, first, count,
+                         hist, stride, outcomes, san, bitmap, digests, partial);
+}
+
+__global__ __launch_bounds__(kOutcomeBlock) void k_starts_replay_san(
+    Board start, u32 stm0, u32 meta0, const DevPos* __restrict__ starts, const uint16_t* __restrict__ clocks,
+    DevPos* __restrict__ finals, const uint16_t* __restrict__ moves, u32 n_games, u32 n_plies, u32 first, u32 count,
+    u64* hist, u32 stride, u64* __restrict__ outcomes, uint8_t* __restrict__ san, u64* __restrict__ bitmap,
+    u64* __restrict__ digests, u64* __restrict__ partial) {
+  replay_san_lane<true>(start, stm0, meta0, 0, starts, clocks, finals, moves, n_games, n_plies, first, count, hist,
+                        stride, outcomes, san, bitmap, digests, partial);
+}
+
+hipError_t launch_replay_san_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
+                                    DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
+                                    u32 count, u64* history, u32 hist_stride, u64* outcomes, uint8_t* san, u64* bitmap,
+                                    u64* digests, u64* partial) {
+  if (count == 0) return hipSuccess;
+  if (first % kOutcomeBlock != 0 || count > hist_stride || (u64)first + count > n_games || !san)
+    return hipErrorInvalidValue;
+  Board b;
+  startpos_board(b);
+  hipLaunchKernelGGL(k_starts_replay_san, dim3(blocks_for(count, kOutcomeBlock)), dim3(kOutcomeBlock), 0, st, b, 0u,
+                     (u32)pack_meta(15, -1), starts, start_halfmoves, finals, moves, n_games, n_plies, first, count,
+                     history, hist_stride, outcomes, san, bitmap, digests, partial);
+  return hipGetLastError();
 }
 
 hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,

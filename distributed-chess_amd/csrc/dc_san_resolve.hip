@@ -5,6 +5,8 @@
 //                   token, find the side to move's pieces that fit it and may
 //                   legally go to its target, write the move word (or a
 //                   flagged word), make the move if there was exactly one
+//   k_starts_san_resolve   the same lane body (san_resolve_lane<true>) from a start
+//                   position per game, and the position each game reached
 //
 // Which piece "Nd2" means is a question of legality (pins, checks, en passant),
 // so the trip runs the validator's analysis once (fpos + analyse) and asks
@@ -93,16 +95,19 @@ __device__ __forceinline__ u32 resolve_stm(const Board& b, u32 meta, u32 tok) {
   return fits == 0 ? MV_NOMATCH : fits > 1 ? MV_AMBIGUOUS : (from | ((u32)t << 6) | (promo << 12));
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(kResolveBlock) void k_san_resolve(Board start, u32 stm0, u32 meta0,
-                                                               const u32* __restrict__ tokens, u32 n_games,
-                                                               u32 n_plies, uint16_t* __restrict__ moves,
-                                                               u32* __restrict__ first_bad, u64* __restrict__ counts) {
+// One lane's game.  STARTS: the game's own start position (starts, may be null:
+// the shared start) and, after the loop, the position after its last resolved
+// move (finals, may be null).  Otherwise the two pointers are not looked at.
+template <bool STARTS>
+__device__ __forceinline__ void san_resolve_lane(Board start, u32 stm0, u32 meta0, const DevPos* __restrict__ starts,
+                                                 DevPos* __restrict__ finals, const u32* __restrict__ tokens,
+                                                 u32 n_games, u32 n_plies, uint16_t* __restrict__ moves,
+                                                 u32* __restrict__ first_bad, u64* __restrict__ counts) {
   const u64 g = (u64)blockIdx.x * kResolveBlock + threadIdx.x;
   const bool active = g < n_games;
   Board b = start;
   u32 stm = stm0, meta = meta0;
+  if (STARTS && active && starts) load_start(starts, g, b, stm, meta);
   u32 bad_at = n_plies;
   u32 n_tok = 0, n_ok = 0, n_nomatch = 0, n_ambiguous = 0, n_malformed = 0;
   for (u32 ply = 0; ply < n_plies; ++ply) {
@@ -127,6 +132,7 @@ __global__ __launch_bounds__(kResolveBlock) void k_san_resolve(Board start, u32 
     if (active) moves[at] = (uint16_t)word;
   }
   if (active && first_bad) first_bad[g] = bad_at;
+  if (STARTS && active && finals) store_final(finals, g, b, stm, meta);
   if (counts) {
     // integers: the order of the waves' adds does not matter
     const u64 s0 = wave_sum64(n_tok), s1 = wave_sum64(n_ok), s2 = wave_sum64(n_nomatch), s3 = wave_sum64(n_ambiguous),
@@ -139,6 +145,33 @@ __global__ __launch_bounds__(kResolveBlock) void k_san_resolve(Board start, u32 
       atomicAdd((unsigned long long*)&counts[4], (unsigned long long)s4);
     }
   }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kResolveBlock) void k_san_resolve(Board start, u32 stm0, u32 meta0,
+                                                               const u32* __restrict__ tokens, u32 n_games,
+                                                               u32 n_plies, uint16_t* __restrict__ moves,
+                                                               u32* __restrict__ first_bad, u64* __restrict__ counts) {
+  san_resolve_lane<false>(start, stm0, meta0, nullptr, nullptr, tokens, n_games, n_plies, moves, first_bad, counts);
+}
+
+__global__ __launch_bounds__(kResolveBlock) void k_starts_san_resolve(
+    Board start, u32 stm0, u32 meta0, const DevPos* __restrict__ starts, DevPos* __restrict__ finals,
+    const u32* __restrict__ tokens, u32 n_games, u32 n_plies, uint16_t* __restrict__ moves,
+    u32* __restrict__ first_bad, u64* __restrict__ counts) {
+  san_resolve_lane<true>(start, stm0, meta0, starts, finals, tokens, n_games, n_plies, moves, first_bad, counts);
+}
+
+hipError_t launch_san_resolve_starts(hipStream_t st, const DevPos* starts, DevPos* finals, const u32* tokens,
+                                     u32 n_games, u32 n_plies, uint16_t* moves, u32* first_bad, u64* counts) {
+  if (n_games == 0) return hipSuccess;
+  if (n_plies && (!tokens || !moves)) return hipErrorInvalidValue;
+  Board b;
+  startpos_board(b);
+  hipLaunchKernelGGL(k_starts_san_resolve, dim3(blocks_for(n_games, kResolveBlock)), dim3(kResolveBlock), 0, st, b, 0u,
+                     (u32)pack_meta(15, -1), starts, finals, tokens, n_games, n_plies, moves, first_bad, counts);
+  return hipGetLastError();
 }
 
 hipError_t launch_san_resolve(hipStream_t st, const DevPos& start, const u32* tokens, u32 n_games, u32 n_plies,

@@ -121,11 +121,19 @@ def lib():
                                         C.POINTER(_Stats)]),
         "dc_replay_outcome_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
                                                C.POINTER(_Stats)]),
+        "dc_replay_outcome_starts": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                               C.POINTER(_Stats), _vp]),
+        "dc_replay_outcome_starts_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                                      C.POINTER(_Stats), _vp]),
         "dc_fen_clocks": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "dc_replay_san": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                     C.POINTER(_Stats)]),
         "dc_replay_san_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            C.POINTER(_Stats)]),
+        "dc_replay_san_starts": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                           C.POINTER(_Stats), _vp]),
+        "dc_replay_san_starts_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                                  C.POINTER(_Stats), _vp]),
         "dc_san_format": (C.c_int, [C.c_uint16, C.c_uint8, _vp]),
         "dc_pgn_movetext": (C.c_int, [_vp, _vp, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint8, C.c_uint8, _vp,
                                       C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -136,6 +144,8 @@ def lib():
                                             C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]),
         "dc_san_resolve": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
         "dc_san_resolve_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+        "dc_san_resolve_starts": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+        "dc_san_resolve_starts_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
         "dc_history_append": (C.c_int, [C.c_char_p, _vp, _vp, C.c_uint32, C.c_size_t, _vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
         "dc_gen_games": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -679,6 +689,114 @@ class Engine:
         sp = np.array([start], POS_DTYPE) if start is not None else None
         _check(lib().dc_san_resolve_device(self.ctx, _ptr(sp), _dptr(d_tokens), n_games, n_plies, _dptr(d_moves),
                                            _dptr(d_first_bad), _ptr(counts)), "dc_san_resolve_device")
+        return counts
+
+    # ---- the per-game-start forms: a start position and a half-move clock per game
+    @staticmethod
+    def _per_game(starts, start_halfmoves, n_games, want_finals):
+        """The *_starts calls' per-game arrays: (starts, clocks, finals), each None or [n_games]."""
+        sp = hm = None
+        if starts is not None:
+            sp = np.ascontiguousarray(starts, POS_DTYPE).reshape(-1)
+            if sp.size != n_games:
+                raise ValueError("starts: one position per game")
+        if start_halfmoves is not None:
+            h = np.asarray(start_halfmoves).reshape(-1)
+            if h.size != n_games:
+                raise ValueError("start_halfmoves: one clock per game")
+            if h.size and (h.min() < 0 or h.max() > 0xFFFF):
+                raise DChessError(EINVAL, "start_halfmoves")
+            hm = np.ascontiguousarray(h, np.uint16)
+        return sp, hm, (np.zeros(n_games, POS_DTYPE) if want_finals else None)
+
+    def replay_outcome_starts(self, moves, starts=None, start_halfmoves=None, want_bitmap=True, want_digests=True,
+                              want_finals=True):
+        """dc_replay_outcome_starts: replay_outcome with game g starting from
+        starts[g] (POS_DTYPE [n_games]; None: the start position) at half-move
+        clock start_halfmoves[g] (None: 0).  Returns replay_outcome's tuple with
+        finals appended: POS_DTYPE [n_games], the position every game stopped
+        in (None if not wanted)."""
+        moves = np.ascontiguousarray(moves, np.uint16)
+        n_plies, n_games = moves.shape
+        words = (n_games + 63) // 64
+        sp, hm, finals = self._per_game(starts, start_halfmoves, n_games, want_finals)
+        out = np.zeros(n_games, OUTCOME_DTYPE)
+        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
+        dig = np.zeros(n_games, np.uint64) if want_digests else None
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        _check(lib().dc_replay_outcome_starts(self.ctx, _ptr(sp), _ptr(hm), _ptr(moves), n_games, n_plies, _ptr(out),
+                                              _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st), _ptr(finals)),
+               "dc_replay_outcome_starts")
+        return out, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}, finals
+
+    def replay_outcome_starts_device(self, d_moves, n_games, n_plies, d_outcomes, d_bitmap=None, d_digests=None,
+                                     d_starts=None, d_start_halfmoves=None, d_finals=None):
+        """dc_replay_outcome_starts_device on DeviceBuffers or raw device addresses
+        (d_starts, d_finals: 40 bytes a game; d_start_halfmoves: 2).  Returns
+        (counts u64[GO_COUNT], stats dict)."""
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        _check(lib().dc_replay_outcome_starts_device(self.ctx, _dptr(d_starts), _dptr(d_start_halfmoves),
+                                                     _dptr(d_moves), n_games, n_plies, _dptr(d_outcomes),
+                                                     _dptr(d_bitmap), _dptr(d_digests), _ptr(counts), C.byref(st),
+                                                     _dptr(d_finals)), "dc_replay_outcome_starts_device")
+        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def replay_san_starts(self, moves, starts=None, start_halfmoves=None, want_bitmap=True, want_digests=True,
+                          want_finals=True):
+        """dc_replay_san_starts: replay_san with per-game starts and clocks (as
+        replay_outcome_starts).  Returns replay_san's tuple with finals appended."""
+        moves = np.ascontiguousarray(moves, np.uint16)
+        n_plies, n_games = moves.shape
+        words = (n_games + 63) // 64
+        sp, hm, finals = self._per_game(starts, start_halfmoves, n_games, want_finals)
+        out = np.zeros(n_games, OUTCOME_DTYPE)
+        san = np.zeros((n_plies, n_games), np.uint8)
+        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
+        dig = np.zeros(n_games, np.uint64) if want_digests else None
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        _check(lib().dc_replay_san_starts(self.ctx, _ptr(sp), _ptr(hm), _ptr(moves), n_games, n_plies, _ptr(out),
+                                          _ptr(san), _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st),
+                                          _ptr(finals)), "dc_replay_san_starts")
+        return out, san, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}, finals
+
+    def replay_san_starts_device(self, d_moves, n_games, n_plies, d_outcomes, d_san, d_bitmap=None, d_digests=None,
+                                 d_starts=None, d_start_halfmoves=None, d_finals=None):
+        """dc_replay_san_starts_device on DeviceBuffers or raw device addresses.
+        Returns (counts u64[GO_COUNT], stats dict)."""
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        _check(lib().dc_replay_san_starts_device(self.ctx, _dptr(d_starts), _dptr(d_start_halfmoves), _dptr(d_moves),
+                                                 n_games, n_plies, _dptr(d_outcomes), _dptr(d_san), _dptr(d_bitmap),
+                                                 _dptr(d_digests), _ptr(counts), C.byref(st), _dptr(d_finals)),
+               "dc_replay_san_starts_device")
+        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def resolve_san_starts(self, tokens, starts=None, want_first_bad=True, want_counts=True, want_finals=True):
+        """dc_san_resolve_starts: resolve_san with game g starting from starts[g]
+        (POS_DTYPE [n_games]; None: the start position).  Returns resolve_san's
+        tuple with finals appended: the position after every game's last
+        resolved move (None if not wanted)."""
+        tokens = np.ascontiguousarray(tokens, np.uint32)
+        n_plies, n_games = tokens.shape
+        sp, _, finals = self._per_game(starts, None, n_games, want_finals)
+        moves = np.zeros((n_plies, n_games), np.uint16)
+        first_bad = np.zeros(n_games, np.uint32) if want_first_bad else None
+        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
+        _check(lib().dc_san_resolve_starts(self.ctx, _ptr(sp), _ptr(tokens), n_games, n_plies, _ptr(moves),
+                                           _ptr(first_bad), _ptr(counts), _ptr(finals)), "dc_san_resolve_starts")
+        return moves, first_bad, counts, finals
+
+    def resolve_san_starts_device(self, d_tokens, n_games, n_plies, d_moves, d_first_bad=None, d_starts=None,
+                                  d_finals=None, want_counts=True):
+        """dc_san_resolve_starts_device on DeviceBuffers or raw device addresses.
+        Returns counts u64[SR_COUNT] (None if not wanted)."""
+        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
+        _check(lib().dc_san_resolve_starts_device(self.ctx, _dptr(d_starts), _dptr(d_tokens), n_games, n_plies,
+                                                  _dptr(d_moves), _dptr(d_first_bad), _ptr(counts),
+                                                  _dptr(d_finals)), "dc_san_resolve_starts_device")
         return counts
 
     def state_hash(self, moves, names, start=None, history=""):

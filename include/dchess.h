@@ -125,6 +125,8 @@ void* dc_ctx_stream(dc_ctx* ctx);
 const char* dc_strerror(int status);
 /* Exact reference error text for verdicts 1..3 (chess.rs:104-121); "" for OK. */
 const char* dc_verdict_message(uint8_t verdict);
+/* 100, or 101 from the library that has the per-game-start calls
+ * (dc_replay_outcome_starts, dc_replay_san_starts, dc_san_resolve_starts). */
 int dc_version(void);
 
 /* Per-kernel HIP-event timing (enable, read, reset).  Kernel names:
@@ -132,7 +134,9 @@ int dc_version(void);
  * "legal_count" (units: positions), "legal_emit" (units: moves); beside them
  * "legal_scan", "legal_fixup" and, for batches of at most 256, "legal_small";
  * "replay_outcome" and "replay_san" (units: moves consumed);
- * "san_resolve" (units: tokens other than DC_SAN_TOKEN_NONE). */
+ * "san_resolve" (units: tokens other than DC_SAN_TOKEN_NONE);
+ * "replay_outcome_starts", "replay_san_starts" and "san_resolve_starts": the
+ * per-game-start forms of those three, same units. */
 int dc_ctx_set_profiling(dc_ctx* ctx, int enable);
 int dc_ctx_kernel_stats(dc_ctx* ctx, const char* kernel, dc_kernel_stats* out);
 int dc_ctx_reset_stats(dc_ctx* ctx);
@@ -314,6 +318,42 @@ int dc_replay_outcome(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove,
 int dc_replay_outcome_device(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, const uint16_t* d_moves,
                              uint32_t n_games, uint32_t n_plies, void* d_outcomes, uint64_t* d_bitmap,
                              uint64_t* d_digests, uint64_t* counts, dc_replay_stats* stats);
+/* dc_replay_outcome with a start position and a half-move clock PER GAME, and
+ * the position each game stopped in: a puzzle set, an opening-suite match file
+ * or a set of adjourned games is one batch, not one batch per start.
+ * starts[g] is game g's start position (starts NULL: every game begins at the
+ * start position); start_halfmoves[g] its half-move clock (NULL: all 0).
+ * Everything else means what it means in dc_replay_outcome: layout,
+ * DC_MOVE_NONE, terminal priority, position identity, occurrences counted from
+ * each game's own start, the chunking, counts and stats.
+ * finals (optional, n_games entries): finals[g] is the position in which game
+ * g stopped -- the one after its last accepted move before end_ply, its start
+ * if none was accepted -- written as dc_apply_batch leaves a dc_pos after the
+ * same accepted moves: stm, castle = the remaining rights, ep = the square
+ * behind a pawn that just moved two ranks or -1, the reserved fields 0.  With
+ * outcomes[g].halfmove it is what dc_pos_to_fen needs, and what a later
+ * *_starts call needs to go on with the game.  Occurrences are counted from
+ * each CALL's start: a continuation knows nothing of the positions before it,
+ * so repeats and a fivefold ending can differ from the unsplit replay's.
+ * Host form: any starts[g].stm > 1 or start_halfmoves[g] > 150 is DC_EINVAL,
+ * found before any device work, nothing written.  n_games == 0 is a
+ * successful no-op; NULL rules as dc_replay_outcome's.
+ * _device form: d_starts, d_start_halfmoves and d_finals are device pointers
+ * like d_moves (each may be NULL, with the meaning above); the host cannot
+ * look into them, so nothing is rejected: a lane takes stm & 1, castle & 15,
+ * an ep outside 0..63 as none (as every DC_RULES_FIDE kernel reads a dc_pos)
+ * and min(start_halfmoves[g], 150) -- a clock above 150 behaves as 150, so the
+ * game is over at ply 0 (seventy-five, unless the start is mate, stalemate or
+ * dead), and the position history is never indexed outside its slots 0..150.
+ * Kernel timing name: "replay_outcome_starts" (units: moves consumed). */
+int dc_replay_outcome_starts(dc_ctx* ctx, const dc_pos* starts, const uint16_t* start_halfmoves,
+                             const uint16_t* moves, uint32_t n_games, uint32_t n_plies, void* outcomes,
+                             uint64_t* bitmap, uint64_t* digests, uint64_t* counts, dc_replay_stats* stats,
+                             dc_pos* finals);
+int dc_replay_outcome_starts_device(dc_ctx* ctx, const dc_pos* d_starts, const uint16_t* d_start_halfmoves,
+                                    const uint16_t* d_moves, uint32_t n_games, uint32_t n_plies, void* d_outcomes,
+                                    uint64_t* d_bitmap, uint64_t* d_digests, uint64_t* counts,
+                                    dc_replay_stats* stats, dc_pos* d_finals);
 /* The half-move clock and full-move number of a FEN (its fifth and sixth
  * fields, which dc_pos_from_fen does not keep), on the host; absent fields
  * give 0 and 1.  Either output may be NULL. */
@@ -359,6 +399,15 @@ int dc_replay_san(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, con
 int dc_replay_san_device(dc_ctx* ctx, const dc_pos* start, uint32_t start_halfmove, const uint16_t* d_moves,
                          uint32_t n_games, uint32_t n_plies, void* d_outcomes, uint8_t* d_san, uint64_t* d_bitmap,
                          uint64_t* d_digests, uint64_t* counts, dc_replay_stats* stats);
+/* dc_replay_san with dc_replay_outcome_starts' per-game starts, clocks and
+ * finals (same meaning, same checks).  Kernel timing name: "replay_san_starts". */
+int dc_replay_san_starts(dc_ctx* ctx, const dc_pos* starts, const uint16_t* start_halfmoves, const uint16_t* moves,
+                         uint32_t n_games, uint32_t n_plies, void* outcomes, uint8_t* san, uint64_t* bitmap,
+                         uint64_t* digests, uint64_t* counts, dc_replay_stats* stats, dc_pos* finals);
+int dc_replay_san_starts_device(dc_ctx* ctx, const dc_pos* d_starts, const uint16_t* d_start_halfmoves,
+                                const uint16_t* d_moves, uint32_t n_games, uint32_t n_plies, void* d_outcomes,
+                                uint8_t* d_san, uint64_t* d_bitmap, uint64_t* d_digests, uint64_t* counts,
+                                dc_replay_stats* stats, dc_pos* d_finals);
 /* The SAN token of one accepted move, on the host: out receives at most 7
  * characters and the NUL.  Piece letter (none for a pawn), origin file and
  * rank as the flags say, "x" for a capture, the target square; a capturing
@@ -476,6 +525,18 @@ int dc_san_resolve(dc_ctx* ctx, const dc_pos* start, const uint32_t* tokens, uin
                    uint16_t* moves, uint32_t* first_bad, uint64_t* counts);
 int dc_san_resolve_device(dc_ctx* ctx, const dc_pos* start, const uint32_t* d_tokens, uint32_t n_games,
                           uint32_t n_plies, uint16_t* d_moves, uint32_t* d_first_bad, uint64_t* counts);
+/* dc_san_resolve with a start position per game (starts NULL: the start
+ * position for all) and, optionally, finals[g] = the position after game g's
+ * last resolved move (its start if none), written as dc_replay_outcome_starts
+ * writes it.  The host form rejects any starts[g].stm > 1 with DC_EINVAL before
+ * any device work; the _device form takes d_starts and d_finals in device
+ * memory and reads stm & 1.  With n_plies == 0 first_bad is all 0 and finals
+ * are the starts.  Kernel timing name: "san_resolve_starts". */
+int dc_san_resolve_starts(dc_ctx* ctx, const dc_pos* starts, const uint32_t* tokens, uint32_t n_games,
+                          uint32_t n_plies, uint16_t* moves, uint32_t* first_bad, uint64_t* counts, dc_pos* finals);
+int dc_san_resolve_starts_device(dc_ctx* ctx, const dc_pos* d_starts, const uint32_t* d_tokens, uint32_t n_games,
+                                 uint32_t n_plies, uint16_t* d_moves, uint32_t* d_first_bad, uint64_t* counts,
+                                 dc_pos* d_finals);
 
 /* Seeded synthetic games: rng = splitmix64 from seed ^ game_id;
  * per ply one draw r: (r & 0xFF) < noise_per_256 -> move (r>>8)&0xFFF, else the

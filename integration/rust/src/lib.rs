@@ -168,6 +168,15 @@ pub mod sys {
                                         d_moves: *const u16, n_games: u32, n_plies: u32, d_outcomes: *mut c_void,
                                         d_bitmap: *mut u64, d_digests: *mut u64, counts: *mut u64,
                                         stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_replay_outcome_starts(ctx: *mut dc_ctx, starts: *const dc_pos, start_halfmoves: *const u16,
+                                        moves: *const u16, n_games: u32, n_plies: u32, outcomes: *mut c_void,
+                                        bitmap: *mut u64, digests: *mut u64, counts: *mut u64,
+                                        stats: *mut dc_replay_stats, finals: *mut dc_pos) -> c_int;
+        pub fn dc_replay_outcome_starts_device(ctx: *mut dc_ctx, d_starts: *const dc_pos,
+                                               d_start_halfmoves: *const u16, d_moves: *const u16, n_games: u32,
+                                               n_plies: u32, d_outcomes: *mut c_void, d_bitmap: *mut u64,
+                                               d_digests: *mut u64, counts: *mut u64, stats: *mut dc_replay_stats,
+                                               d_finals: *mut dc_pos) -> c_int;
         pub fn dc_fen_clocks(fen: *const c_char, halfmove: *mut u32, fullmove: *mut u32) -> c_int;
         // notation
         pub fn dc_replay_san(ctx: *mut dc_ctx, start: *const dc_pos, start_halfmove: u32, moves: *const u16,
@@ -177,6 +186,15 @@ pub mod sys {
                                     d_moves: *const u16, n_games: u32, n_plies: u32, d_outcomes: *mut c_void,
                                     d_san: *mut u8, d_bitmap: *mut u64, d_digests: *mut u64, counts: *mut u64,
                                     stats: *mut dc_replay_stats) -> c_int;
+        pub fn dc_replay_san_starts(ctx: *mut dc_ctx, starts: *const dc_pos, start_halfmoves: *const u16,
+                                    moves: *const u16, n_games: u32, n_plies: u32, outcomes: *mut c_void,
+                                    san: *mut u8, bitmap: *mut u64, digests: *mut u64, counts: *mut u64,
+                                    stats: *mut dc_replay_stats, finals: *mut dc_pos) -> c_int;
+        pub fn dc_replay_san_starts_device(ctx: *mut dc_ctx, d_starts: *const dc_pos, d_start_halfmoves: *const u16,
+                                           d_moves: *const u16, n_games: u32, n_plies: u32, d_outcomes: *mut c_void,
+                                           d_san: *mut u8, d_bitmap: *mut u64, d_digests: *mut u64,
+                                           counts: *mut u64, stats: *mut dc_replay_stats,
+                                           d_finals: *mut dc_pos) -> c_int;
         pub fn dc_san_format(move_: u16, san: u8, out: *mut c_char) -> c_int;
         pub fn dc_pgn_movetext(moves: *const u16, san: *const u8, n_plies: u32, stride: usize, first_fullmove: u32,
                                first_stm: u8, result: u8, out: *mut c_char, out_cap: usize,
@@ -193,6 +211,12 @@ pub mod sys {
         pub fn dc_san_resolve_device(ctx: *mut dc_ctx, start: *const dc_pos, d_tokens: *const u32, n_games: u32,
                                      n_plies: u32, d_moves: *mut u16, d_first_bad: *mut u32,
                                      counts: *mut u64) -> c_int;
+        pub fn dc_san_resolve_starts(ctx: *mut dc_ctx, starts: *const dc_pos, tokens: *const u32, n_games: u32,
+                                     n_plies: u32, moves: *mut u16, first_bad: *mut u32, counts: *mut u64,
+                                     finals: *mut dc_pos) -> c_int;
+        pub fn dc_san_resolve_starts_device(ctx: *mut dc_ctx, d_starts: *const dc_pos, d_tokens: *const u32,
+                                            n_games: u32, n_plies: u32, d_moves: *mut u16, d_first_bad: *mut u32,
+                                            counts: *mut u64, d_finals: *mut dc_pos) -> c_int;
         pub fn dc_replay_info(ctx: *mut dc_ctx, rules: u32, start: *const dc_pos, moves: *const u16, n_games: u32,
                               n_plies: u32, bitmap: *mut u64, digests: *mut u64, info: *mut u8,
                               stats: *mut dc_replay_stats) -> c_int;
@@ -417,6 +441,30 @@ impl Engine {
                                               std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
                                               &mut st) }, "dc_replay_outcome")?;
         Ok((out, st))
+    }
+
+    /// A batch of games that each begin at their own position with their own
+    /// half-move clock (dc_replay_outcome_starts): `moves` is ply-major
+    /// [n_plies][n_games], n_games = starts.len() = start_halfmoves.len().
+    /// Returns every game's outcome and the position it stopped in, which with
+    /// the outcome's halfmove continues the game in a later call.
+    pub fn replay_outcome_starts(&self, starts: &[sys::dc_pos], start_halfmoves: &[u16], moves: &[u16])
+                                 -> Result<(Vec<sys::dc_game_outcome>, Vec<sys::dc_pos>), DcError> {
+        let bad = |text: &str| DcError { status: sys::DC_EINVAL, what: "dc_replay_outcome_starts", text: text.into() };
+        let n_games = u32::try_from(starts.len()).map_err(|_| bad("more than u32::MAX games"))?;
+        if start_halfmoves.len() != starts.len() { return Err(bad("one clock per start")); }
+        if n_games == 0 { return Ok((Vec::new(), Vec::new())); }
+        if moves.len() % starts.len() != 0 { return Err(bad("moves is not [n_plies][n_games]")); }
+        let n_plies = u32::try_from(moves.len() / starts.len()).map_err(|_| bad("more than u32::MAX plies"))?;
+        let mut out = vec![sys::dc_game_outcome::default(); starts.len()];
+        let mut finals = starts.to_vec();
+        check(unsafe { sys::dc_replay_outcome_starts(self.0, starts.as_ptr(), start_halfmoves.as_ptr(),
+                                                     moves.as_ptr(), n_games, n_plies,
+                                                     out.as_mut_ptr() as *mut c_void, std::ptr::null_mut(),
+                                                     std::ptr::null_mut(), std::ptr::null_mut(),
+                                                     std::ptr::null_mut(), finals.as_mut_ptr()) },
+              "dc_replay_outcome_starts")?;
+        Ok((out, finals))
     }
 
     /// One game's move log under the standard rules as PGN movetext

@@ -2,15 +2,17 @@
 """Replays a PGN file on the GPU.
 
 Splits FILE into games (dchess.pgn_games), parses each game's movetext into
-SAN tokens (dc_pgn_parse_movetext), batches the games that share a start
-position (the FEN tag through dc_pos_from_fen / dc_fen_clocks, else the start
-position; columns padded with SAN_TOKEN_NONE), resolves the tokens to move
-words (dc_san_resolve) and replays those under the standard rules
-(dc_replay_san).  Prints the histogram of adjudicated outcomes, the games in
+SAN tokens (dc_pgn_parse_movetext), puts all games into one batch, each with
+its own start position and half-move clock (the FEN tag through
+dc_pos_from_fen / dc_fen_clocks, else the start position; columns padded with
+SAN_TOKEN_NONE), resolves the tokens to move words (dc_san_resolve_starts) and
+replays those under the standard rules (dc_replay_san_starts): two calls a
+file, whatever its FEN tags.  Prints the histogram of adjudicated outcomes, the games in
 which a token did not resolve (with the token's number and why), the games
 whose movetext is not SAN, and the games whose adjudicated result contradicts
 their Result tag.  A game the board does not decide (a resignation, an agreed
-draw, an unfinished game) contradicts nothing.
+draw, an unfinished game) contradicts nothing.  With --final-fen, also the FEN
+of the position every game stopped in.
 
     python tools/games_pgn.py --games 100 --plies 400 > games.pgn
     python tools/pgn_replay.py games.pgn
@@ -48,25 +50,37 @@ def load(text):
 
 
 def replay(eng, games):
-    """Resolves and replays the games, one batch per start position.  Returns
-    {index: (moves u16 [n_tokens], first_bad, outcome record)}."""
-    groups = {}
-    for g in games:
-        groups.setdefault(g[1].get("FEN"), []).append(g)
-    done = {}
-    for fen, members in groups.items():
-        start, halfmove = None, 0
+    """Resolves and replays the games in one batch, every game from its own start
+    (one resolve_san_starts call and one replay_san_starts call, whatever the FEN tags).
+    Returns {index: (moves u16 [n_tokens], first_bad, outcome record, final FEN)}."""
+    n = len(games)
+    starts = np.array([dchess.startpos()] * n, dchess.POS_DTYPE)
+    halfmoves, fullmoves = np.zeros(n, np.uint16), [1] * n
+    for k, g in enumerate(games):
+        fen = g[1].get("FEN")
         if fen is not None:
-            start = dchess.pos_from_fen(fen)
-            halfmove = min(dchess.fen_clocks(fen)[0], 150)
-        n_plies = max(max(len(m[2]) for m in members), 1)
-        tokens = np.full((n_plies, len(members)), dchess.SAN_TOKEN_NONE, np.uint32)
-        for k, m in enumerate(members):
-            tokens[:len(m[2]), k] = m[2]
-        moves, first_bad, _ = eng.resolve_san(tokens, start)
-        out = eng.replay_san(moves, start, halfmove, want_bitmap=False, want_digests=False)[0]
-        for k, m in enumerate(members):
-            done[m[0]] = (moves[:len(m[2]), k].copy(), int(first_bad[k]), out[k])
+            starts[k] = dchess.pos_from_fen(fen)
+            halfmove, fullmoves[k] = dchess.fen_clocks(fen)
+            halfmoves[k] = min(halfmove, 150)
+    # columns ordered by side to move: a wave that holds both sides runs both sides'
+    # rule code one after the other (DESIGN 3.15); the results are keyed by game
+    order = np.argsort(starts["stm"], kind="stable")
+    games = [games[k] for k in order]
+    starts, halfmoves, fullmoves = starts[order], halfmoves[order], [fullmoves[k] for k in order]
+    n_plies = max(max(len(g[2]) for g in games), 1)
+    tokens = np.full((n_plies, n), dchess.SAN_TOKEN_NONE, np.uint32)
+    for k, g in enumerate(games):
+        tokens[:len(g[2]), k] = g[2]
+    moves, first_bad, _, _ = eng.resolve_san_starts(tokens, starts, want_finals=False)
+    out, san, _, _, _, _, finals = eng.replay_san_starts(moves, starts, halfmoves, want_bitmap=False,
+                                                         want_digests=False)
+    done = {}
+    played = (san != 0xFF).sum(axis=0)
+    for k, g in enumerate(games):
+        # Black's move completes a full move
+        fullmove = fullmoves[k] + (int(starts[k]["stm"]) + int(played[k])) // 2
+        fen = dchess.pos_to_fen(finals[k], int(out[k]["halfmove"]), fullmove)
+        done[g[0]] = (moves[:len(g[2]), k].copy(), int(first_bad[k]), out[k], fen)
     return done
 
 
@@ -74,6 +88,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("file")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--final-fen", action="store_true", help="print the FEN of the position every game stopped in")
     a = ap.parse_args()
     with open(a.file, encoding="utf-8") as f:
         games, broken = load(f.read())
@@ -83,7 +98,7 @@ def main():
 
     print(f"{len(games) + len(broken)} games, {len(games)} parsed, {len(broken)} not")
     hist = np.zeros(dchess.GO_COUNT, np.int64)
-    for _, _, out in done.values():
+    for _, _, out, _ in done.values():
         hist[int(out["result"])] += 1
     for k, name in enumerate(dchess.GO_NAMES):
         print(f"  {name:12s} {int(hist[k])}")
@@ -91,7 +106,7 @@ def main():
         print(f"game {i + 1}: {msg}")
     unresolved = contradicted = 0
     for i, tags, tokens, tag in games:
-        moves, first_bad, out = done[i]
+        moves, first_bad, out, _ = done[i]
         if first_bad < len(tokens):
             unresolved += 1
             print(f"game {i + 1}: move {first_bad + 1} of {len(tokens)} did not resolve "
@@ -102,6 +117,9 @@ def main():
             print(f"game {i + 1}: Result \"{tag}\" but the board says {dchess.GO_NAMES[result]} "
                   f"after {int(out['end_ply'])} of {len(tokens)} moves")
     print(f"{unresolved} games with an unresolved move, {contradicted} with a contradicted result")
+    if a.final_fen:
+        for i, _, _, _ in games:
+            print(f"game {i + 1}: {done[i][3]}")
     return 1 if broken or unresolved or contradicted else 0
 
 
