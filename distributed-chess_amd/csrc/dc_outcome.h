@@ -17,31 +17,49 @@ constexpr u32 kOutcomeRecord = 5 + kOutcomeResults;
 // u64 words of position history for `games` lanes, laid out [slot][word][game].
 inline size_t outcome_history_words(u32 games) { return (size_t)kOutcomeSlots * kOutcomeKeyWords * games; }
 
-// Adjudicates games [first, first + count) of the batch (first a multiple of
-// kOutcomeBlock): outcomes, digests, the bitmap's word columns and the block
-// records of those games.  history holds outcome_history_words(hist_stride)
-// words, hist_stride >= count.
-hipError_t launch_replay_outcome(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
-                                 u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
-                                 u64* outcomes, u64* bitmap, u64* digests, u64* partial);
-// The same (k_replay_san, dc_san.hip) plus san: ply-major [n_plies][n_games]
-// SAN bytes (DC_SAN_*), 0xFF where no move was made.  Same history, same records.
-hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
-                             u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
-                             u64* outcomes, uint8_t* san, u64* bitmap, u64* digests, u64* partial);
-// The per-game-start forms (k_starts_replay_outcome, k_starts_replay_san): game g
-// starts from starts[g] with clock min(start_halfmoves[g], 150) (null: the start
-// position, clock 0) and leaves the position it stopped in in finals[g] (null:
-// not wanted).  All three are indexed by the game, whatever `first` is.  The
-// rest as above.
-hipError_t launch_replay_outcome_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
-                                        DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
-                                        u32 count, u64* history, u32 hist_stride, u64* outcomes, u64* bitmap,
-                                        u64* digests, u64* partial);
-hipError_t launch_replay_san_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
-                                    DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
-                                    u32 count, u64* history, u32 hist_stride, u64* outcomes, uint8_t* san, u64* bitmap,
-                                    u64* digests, u64* partial);
+// One launch's batch arguments: games [first, first + count) of the batch
+// (first a multiple of kOutcomeBlock) get their outcomes, digests, the bitmap's
+// word columns and block records.  history holds
+// outcome_history_words(hist_stride) words, hist_stride >= count.  san: ply-major
+// [n_plies][n_games] SAN bytes (DC_SAN_*), 0xFF where no move was made; only
+// launch_replay_san looks at it.  bitmap and digests may be null.
+struct OutcomeBatch {
+  const uint16_t* moves;
+  u32 n_games, n_plies, first, count;
+  u64* history;
+  u32 hist_stride;
+  u64* outcomes;
+  uint8_t* san;
+  u64* bitmap;
+  u64* digests;
+  u64* partial;
+};
+// The per-game arrays, in device memory: game g starts from starts[g] with clock
+// min(clocks[g], 150) (null: the shared start, clock 0) and leaves the position
+// it stopped in in finals[g] (null: not wanted).  All three are indexed by the
+// game, whatever `first` is.
+struct OutcomePerGame {
+  const DevPos* starts;
+  const uint16_t* clocks;
+  DevPos* finals;
+};
+
+// The launchers' one argument check; start_halfmove is the shared clock (0 with
+// per-game arrays).
+inline bool outcome_batch_ok(const OutcomeBatch& a, u32 start_halfmove, bool want_san) {
+  return a.first % kOutcomeBlock == 0 && a.count <= a.hist_stride && start_halfmove < kOutcomeSlots &&
+         (u64)a.first + a.count <= a.n_games && (a.san || !want_san);
+}
+
+// Adjudicates the batch's games from `start` at clock start_halfmove
+// (k_replay_outcome), or with per_game from their own starts and clocks
+// (k_starts_replay_outcome, which ignores start_halfmove).
+hipError_t launch_replay_outcome(hipStream_t st, const DevPos& start, u32 start_halfmove,
+                                 const OutcomePerGame* per_game, const OutcomeBatch& a);
+// The same plus a.san (k_replay_san, k_starts_replay_san: dc_san.hip).  Same
+// history, same records.
+hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const OutcomePerGame* per_game,
+                             const OutcomeBatch& a);
 // totals[kOutcomeRecord] =the n_blocks block records combined (xor for the digest xor).
 hipError_t launch_outcome_reduce(hipStream_t st, const u64* partial, u32 n_blocks, u64* totals);
 

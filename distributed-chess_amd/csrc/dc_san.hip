@@ -1,11 +1,11 @@
 // dc_san.hip -- k_replay_outcome's adjudicating replay (dc_outcome.hip) that also
 // says what was played: one SAN byte per accepted ply (include/dchess.h DC_SAN_*).
 //
-//   k_replay_san   one lane per game; the loop, the position history, the
-//                  chunking and the block records are k_replay_outcome's (its
-//                  loop is repeated here so that kernel's code stays as it is;
-//                  k_outcome_reduce combines the records of either)
-//   k_starts_replay_san   the same lane body (replay_san_lane<true>) with
+//   k_replay_san   one lane per game; the loop (dc_outcome_lane.h, SAN), the
+//                  position history, the chunking and the block records are
+//                  k_replay_outcome's (k_outcome_reduce combines the records
+//                  of either)
+//   k_starts_replay_san   the same lane body (STARTS) with
 //                  k_starts_replay_outcome's per-game starts, clocks and finals
 //
 // The byte of ply p has two halves.  Kind, capture and the disambiguation
@@ -18,209 +18,9 @@
 // generation, one byte store per ply.
 #include <hip/hip_runtime.h>
 
-#include "dc_common.h"
-#include "dc_outcome.h"
+#include "dc_outcome_lane.h"
 
 namespace dc {
-
-namespace {
-
-enum : u32 { GO_ONGOING = 0, GO_WHITE_WINS, GO_BLACK_WINS, GO_STALEMATE, GO_DEAD, GO_FIVEFOLD, GO_SEVENTYFIVE };
-constexpr u32 kClockEnd = kOutcomeSlots - 1;  // 150 half-moves: the 75-move rule
-enum : u32 { SAN_CAPTURE = 8, SAN_FILE = 16, SAN_RANK = 32, SAN_CHECK = 64, SAN_MATE = 128, SAN_NONE = 0xFF };
-
-__device__ __forceinline__ u64* key_at(u64* hist, u32 slot, u32 stride, u32 lane_game) {
-  return hist + (size_t)slot * kOutcomeKeyWords * stride + lane_game;
-}
-
-// fide_verdict_stm (dc_fide_rules.h) == V_OK, and for an accepted move the low
-// six bits of its SAN byte.  Disambiguation (FIDE C.10.3): `others` = the other
-// pieces of the mover's kind and colour that attack t (a reverse attack from t)
-// and may legally go there.  The played move is legal, so t is not ours and,
-// in check, t resolves the check: an unpinned attacker of t is legal.  A pinned
-// one is legal only out of check and along its pin line, i.e. when it stands on
-// the line through the king and t.
-template <int STM>
-__device__ __forceinline__ bool san_verdict_stm(const Board& b, u32 meta, u32 m, u32& low) {
-  typedef FDir<STM> FD;
-  const int s = (int)(m & 63), t = (int)((m >> 6) & 63);
-  const u32 promo = (m >> 12) & 7;
-  const FPos<STM> f = fpos<STM>(b);
-  const Analysis a = analyse<STM>(f);
-  const u64 targets = fide_piece_targets<STM>(b, meta, f, a, s);
-  if (!((targets >> t) & 1)) return false;
-  const u64 from = 1ull << s;
-  const bool pawn = (from & f.P) != 0;
-  const bool is_promo = pawn && ((1ull << t) & FD::LAST);
-  if (is_promo ? (promo < 1 || promo > 4) : (promo != 0)) return false;
-  const u64 q = f.O & f.D;
-  const bool orth = (from & f.O) != 0, diag = (from & f.D) != 0;
-  const u32 kind = pawn ? 0u : (from & f.N) ? 1u : (from & f.K) ? 5u : (orth && diag) ? 4u : orth ? 3u : 2u;
-  const u64 same = ((from & f.N) ? f.N : (orth && diag) ? q : orth ? (f.O & ~q) : diag ? (f.D & ~q) : 0ull) & ~from;
-  u32 flags = ((f.occ >> t) & 1) || (pawn && t == meta_ep(meta)) ? SAN_CAPTURE : 0u;
-  // the pieces of the kind that stand a knight's move from t, or on a line of their kind through
-  // t: rare, so the blockers are looked at only for those
-  const Lines l = lines_of(t);
-  const u64 near = (from & f.N) ? knight_attacks(1ull << t)
-                                : ((orth ? (l.file | l.rank) : 0ull) | (diag ? (l.diag | l.anti) : 0ull));
-  if (same & near) {
-    u64 att = (from & f.N) ? near : 0ull;
-    if (orth) att |= line_attacks(t, l.file, f.occ) | line_attacks(t, l.rank, f.occ);
-    if (diag) att |= line_attacks(t, l.diag, f.occ) | line_attacks(t, l.anti, f.occ);
-    const u64 along = (a.checkers || a.ksq < 0) ? 0ull : line_through(a.ksq, t);
-    const u64 others = att & same & (~a.pinned | along);
-    if (others) {
-      const bool on_file = (others & (kFileA << (s & 7))) != 0;
-      const bool on_rank = (others & (0xFFull << (s & 56))) != 0;
-      flags |= !on_file ? SAN_FILE : !on_rank ? SAN_RANK : (SAN_FILE | SAN_RANK);
-    }
-  }
-  low = kind | flags;
-  return true;
-}
-
-// fide_verdict's gates (out of range, no piece, wrong turn), then the above.
-__device__ __forceinline__ bool san_verdict(const Board& b, u32 stm, u32 meta, u32 m, u32& low) {
-  if (m & 0x8000u) return false;
-  const u32 nib = nibble(b, (int)(m & 63));
-  if ((nib >> 1) == 0 || (nib & 1) != stm) return false;
-  return stm ? san_verdict_stm<1>(b, meta, m, low) : san_verdict_stm<0>(b, meta, m, low);
-}
-
-// One lane's replay; STARTS, starts, clocks and finals as replay_outcome_lane's
-// (dc_outcome.hip).
-template <bool STARTS>
-__device__ __forceinline__ void replay_san_lane(Board start, u32 stm0, u32 meta0, u32 clock0,
-                                                const DevPos* __restrict__ starts, const uint16_t* __restrict__ clocks,
-                                                DevPos* __restrict__ finals, const uint16_t* __restrict__ moves,
-                                                u32 n_games, u32 n_plies, u32 first, u32 count, u64* hist, u32 stride,
-                                                u64* __restrict__ outcomes, uint8_t* __restrict__ san,
-                                                u64* __restrict__ bitmap, u64* __restrict__ digests,
-                                                u64* __restrict__ partial) {
-  const u32 local = blockIdx.x * kOutcomeBlock + threadIdx.x;  // the lane's column of the history
-  const u32 g = first + local;
-  const bool active = local < count;
-  const u32 words = (n_games + 63) >> 6;
-  Board b = start;
-  u32 stm = stm0, meta = meta0;
-  u32 clock = clock0;  // half-move clock
-  if (STARTS && active) {
-    if (starts) load_start(starts, g, b, stm, meta);
-    if (clocks) clock = min((u32)clocks[g], kClockEnd);  // the history has slots 0..150
-  }
-  u32 base = clock;  // the clock this run of reversible moves began with
-  u32 result = GO_ONGOING, repeats = 1, consumed = 0, end_ply = n_plies;
-  u32 validated = 0, accepted = 0;
-  u32 low = 0;          // kind | capture | file | rank of the last accepted move (ply consumed - 1)
-  bool fresh = active;  // the position has not been adjudicated yet
-  u32 ply = 0;
-  for (;; ++ply) {
-    u32 byte = SAN_NONE;  // of ply - 1: no move unless this trip adjudicates what it led to
-    if (fresh) {
-      fresh = false;
-      u64 checkers;
-      const u32 n_legal = stm ? fide_count_checkers<1>(b, meta, checkers) : fide_count_checkers<0>(b, meta, checkers);
-      // the move that led here is complete now: it gives check, it mates
-      byte = low | (checkers ? SAN_CHECK : 0u) | (checkers && n_legal == 0 ? SAN_MATE : 0u);
-      u32 kw = (meta & 15) | (stm << 11);
-      if (meta & META_EP_VALID) {
-        const bool usable = stm ? fide_ep_capturable<1>(b, meta) : fide_ep_capturable<0>(b, meta);
-        kw |= usable ? (meta & 0x7F0u) : 0u;
-      }
-      repeats = 1;
-      for (int s = (int)clock - 2; s >= (int)base; s -= 2) {
-        const u64* k = key_at(hist, (u32)s, stride, local);
-        if (k[2 * (size_t)stride] == b.b2) {
-          const bool same = k[0] == b.b0 && k[stride] == b.b1 && k[3 * (size_t)stride] == b.b3 &&
-                            k[4 * (size_t)stride] == (u64)kw;
-          repeats += same ? 1u : 0u;
-        }
-      }
-      if (clock <= kClockEnd) {
-        u64* k = key_at(hist, clock, stride, local);
-        k[0] = b.b0;
-        k[stride] = b.b1;
-        k[2 * (size_t)stride] = b.b2;
-        k[3 * (size_t)stride] = b.b3;
-        k[4 * (size_t)stride] = kw;
-      }
-      // checkmate > stalemate > dead > fivefold > seventy-five
-      result = n_legal == 0 ? (checkers ? (stm ? GO_WHITE_WINS : GO_BLACK_WINS) : GO_STALEMATE)
-               : fide_insufficient(b) ? GO_DEAD
-               : repeats >= 5       ? GO_FIVEFOLD
-               : clock >= kClockEnd ? GO_SEVENTYFIVE
-                                    : GO_ONGOING;
-      if (result != GO_ONGOING) end_ply = consumed;
-    }
-    // one store a trip and a whole row segment a wave: the byte of the ply before
-    if (active && ply) san[(size_t)(ply - 1) * n_games + g] = (uint8_t)byte;
-    if (ply >= n_plies) break;
-    const bool live = active && result == GO_ONGOING;
-    if (ballot(live) == 0) break;  // every game of the wave has ended (a ballot is wave-uniform)
-    const u32 m = live ? moves[(size_t)ply * n_games + g] : 0xFFFFu;
-    bool ok = false;
-    if (m != 0xFFFFu) {
-      ++validated;
-      ok = san_verdict(b, stm, meta, m, low);
-      if (ok) {
-        const int f = (int)(m & 63), t = (int)((m >> 6) & 63);
-        // a pawn move (en passant included) or a capture restarts the clock
-        const bool reset = (nibble(b, f) >> 1) == KC_P || ((occupied(b) >> t) & 1);
-        meta = fide_make_rt(b, stm, meta, f, t, (int)((m >> 12) & 7));
-        stm ^= 1;
-        ++accepted;
-        clock = reset ? 0u : clock + 1;
-        base = reset ? 0u : base;
-        consumed = ply + 1;
-        fresh = true;
-      }
-    }
-    const u64 word = ballot(ok);
-    if (bitmap && lane_id() == 0 && (g >> 6) < words) bitmap[(size_t)ply * words + (g >> 6)] = word;
-  }
-  // the plies no game of the wave reached: no SAN, accept bits 0
-  if (active)
-    for (u32 p = ply; p < n_plies; ++p) san[(size_t)p * n_games + g] = (uint8_t)SAN_NONE;
-  if (bitmap && ((first + (local & ~63u)) >> 6) < words) {
-    const u32 w = (first + (local & ~63u)) >> 6;
-    for (u32 p = ply + lane_id(); p < n_plies; p += 64) bitmap[(size_t)p * words + w] = 0;
-  }
-  u64 d = 0;
-  if (active) {
-    d = board_digest(b, stm);
-    if (digests) digests[g] = d;
-    outcomes[g] = (u64)result | ((u64)min(repeats, 255u) << 8) | ((u64)(clock & 0xFFFFu) << 16) | ((u64)end_ply << 32);
-    if (STARTS && finals) store_final(finals, g, b, stm, meta);
-  }
-  // the block's record (k_replay_outcome's)
-  __shared__ u64 ws[kOutcomeBlock / 64][kOutcomeRecord];
-  const u64 sv = wave_sum64(validated), sa = wave_sum64(accepted), sd = wave_sum64(d);
-  u64 x = d;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o, 64);
-  u64 by_result[kOutcomeResults];
-#pragma unroll
-  for (u32 k = 0; k < kOutcomeResults; ++k) by_result[k] = pc(ballot(active && result == k));
-  const u32 w = threadIdx.x >> 6;
-  if (lane_id() == 0) {
-    ws[w][0] = sv;
-    ws[w][1] = sa;
-    ws[w][2] = sv - sa;
-    ws[w][3] = sd;
-    ws[w][4] = x;
-#pragma unroll
-    for (u32 k = 0; k < kOutcomeResults; ++k) ws[w][5 + k] = by_result[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kOutcomeRecord) {
-    const u32 k = threadIdx.x;
-    u64 v = ws[0][k];
-    for (u32 q = 1; q < kOutcomeBlock / 64; ++q) v = (k == 4) ? (v ^ ws[q][k]) : (v + ws[q][k]);
-    partial[((size_t)(first / kOutcomeBlock) + blockIdx.x) * kOutcomeRecord + k] = v;
-  }
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(kOutcomeBlock) void k_replay_san(Board start, u32 stm0, u32 meta0, u32 clock0,
                                                               const uint16_t* __restrict__ moves, u32 n_games,
@@ -228,8 +28,8 @@ __global__ __launch_bounds__(kOutcomeBlock) void k_replay_san(Board start, u32 s
                                                               u64* __restrict__ outcomes, uint8_t* __restrict__ san,
                                                               u64* __restrict__ bitmap, u64* __restrict__ digests,
                                                               u64* __restrict__ partial) {
-  replay_san_lane<false>(start, stm0, meta0, clock0, nullptr, nullptr, nullptr, moves, n_games, n_plies, first, count,
-                         hist, stride, outcomes, san, bitmap, digests, partial);
+  replay_adjudicate_lane<false, true>(start, stm0, meta0, clock0, nullptr, nullptr, nullptr, moves, n_games, n_plies,
+                                      first, count, hist, stride, outcomes, san, bitmap, digests, partial);
 }
 
 __global__ __launch_bounds__(kOutcomeBlock) void k_starts_replay_san(
@@ -237,36 +37,24 @@ __global__ __launch_bounds__(kOutcomeBlock) void k_starts_replay_san(
     DevPos* __restrict__ finals, const uint16_t* __restrict__ moves, u32 n_games, u32 n_plies, u32 first, u32 count,
     u64* hist, u32 stride, u64* __restrict__ outcomes, uint8_t* __restrict__ san, u64* __restrict__ bitmap,
     u64* __restrict__ digests, u64* __restrict__ partial) {
-  replay_san_lane<true>(start, stm0, meta0, 0, starts, clocks, finals, moves, n_games, n_plies, first, count, hist,
-                        stride, outcomes, san, bitmap, digests, partial);
+  replay_adjudicate_lane<true, true>(start, stm0, meta0, 0, starts, clocks, finals, moves, n_games, n_plies, first,
+                                     count, hist, stride, outcomes, san, bitmap, digests, partial);
 }
 
-hipError_t launch_replay_san_starts(hipStream_t st, const DevPos* starts, const uint16_t* start_halfmoves,
-                                    DevPos* finals, const uint16_t* moves, u32 n_games, u32 n_plies, u32 first,
-                                    u32 count, u64* history, u32 hist_stride, u64* outcomes, uint8_t* san, u64* bitmap,
-                                    u64* digests, u64* partial) {
-  if (count == 0) return hipSuccess;
-  if (first % kOutcomeBlock != 0 || count > hist_stride || (u64)first + count > n_games || !san)
-    return hipErrorInvalidValue;
-  Board b;
-  startpos_board(b);
-  hipLaunchKernelGGL(k_starts_replay_san, dim3(blocks_for(count, kOutcomeBlock)), dim3(kOutcomeBlock), 0, st, b, 0u,
-                     (u32)pack_meta(15, -1), starts, start_halfmoves, finals, moves, n_games, n_plies, first, count,
-                     history, hist_stride, outcomes, san, bitmap, digests, partial);
-  return hipGetLastError();
-}
-
-hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const uint16_t* moves,
-                             u32 n_games, u32 n_plies, u32 first, u32 count, u64* history, u32 hist_stride,
-                             u64* outcomes, uint8_t* san, u64* bitmap, u64* digests, u64* partial) {
-  if (count == 0) return hipSuccess;
-  if (first % kOutcomeBlock != 0 || count > hist_stride || start_halfmove >= kOutcomeSlots ||
-      (u64)first + count > n_games || !san)
-    return hipErrorInvalidValue;
+hipError_t launch_replay_san(hipStream_t st, const DevPos& start, u32 start_halfmove, const OutcomePerGame* per_game,
+                             const OutcomeBatch& a) {
+  if (a.count == 0) return hipSuccess;
+  if (!outcome_batch_ok(a, per_game ? 0 : start_halfmove, true)) return hipErrorInvalidValue;
+  const dim3 grid(blocks_for(a.count, kOutcomeBlock)), block(kOutcomeBlock);
   const Board b{start.bb[0], start.bb[1], start.bb[2], start.bb[3]};
-  hipLaunchKernelGGL(k_replay_san, dim3(blocks_for(count, kOutcomeBlock)), dim3(kOutcomeBlock), 0, st, b,
-                     (u32)(start.stm & 1), (u32)pack_meta(start.castle, start.ep), start_halfmove, moves, n_games,
-                     n_plies, first, count, history, hist_stride, outcomes, san, bitmap, digests, partial);
+  const u32 stm = start.stm & 1, meta = pack_meta(start.castle, start.ep);
+  if (per_game)
+    hipLaunchKernelGGL(k_starts_replay_san, grid, block, 0, st, b, stm, meta, per_game->starts, per_game->clocks,
+                       per_game->finals, a.moves, a.n_games, a.n_plies, a.first, a.count, a.history, a.hist_stride,
+                       a.outcomes, a.san, a.bitmap, a.digests, a.partial);
+  else
+    hipLaunchKernelGGL(k_replay_san, grid, block, 0, st, b, stm, meta, start_halfmove, a.moves, a.n_games, a.n_plies,
+                       a.first, a.count, a.history, a.hist_stride, a.outcomes, a.san, a.bitmap, a.digests, a.partial);
   return hipGetLastError();
 }
 

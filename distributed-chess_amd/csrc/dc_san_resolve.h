@@ -11,12 +11,11 @@ constexpr u32 kResolveCounts = 5;   // DC_SR_COUNT
 // "notation input"): moves [n_plies][n_games] move words or flagged words,
 // first_bad[n_games] (may be null), counts[kResolveCounts] (may be null; the
 // kernel ADDS to it, one atomic per wave and counter: zero it first).
-hipError_t launch_san_resolve(hipStream_t st, const DevPos& start, const u32* tokens, u32 n_games, u32 n_plies,
-                              uint16_t* moves, u32* first_bad, u64* counts);
-// The per-game-start form (k_starts_san_resolve): game g starts from starts[g]
-// (null: the start position) and leaves the position after its last resolved
-// move in finals[g] (null: not wanted).  n_plies == 0 copies the starts.
-hipError_t launch_san_resolve_starts(hipStream_t st, const DevPos* starts, DevPos* finals, const u32* tokens,
-                                     u32 n_games, u32 n_plies, uint16_t* moves, u32* first_bad, u64* counts);
+// per_game (k_starts_san_resolve): game g starts from starts[g] (null: `start`)
+// and leaves the position after its last resolved move in finals[g] (null: not
+// wanted); n_plies == 0 copies the starts.  Otherwise the two are not looked at.
+hipError_t launch_san_resolve(hipStream_t st, const DevPos& start, bool per_game, const DevPos* starts, DevPos* finals,
+                              const u32* tokens, u32 n_games, u32 n_plies, uint16_t* moves, u32* first_bad,
+                              u64* counts);
 
 }  // namespace dc

@@ -163,25 +163,20 @@ __global__ __launch_bounds__(kResolveBlock) void k_starts_san_resolve(
   san_resolve_lane<true>(start, stm0, meta0, starts, finals, tokens, n_games, n_plies, moves, first_bad, counts);
 }
 
-hipError_t launch_san_resolve_starts(hipStream_t st, const DevPos* starts, DevPos* finals, const u32* tokens,
-                                     u32 n_games, u32 n_plies, uint16_t* moves, u32* first_bad, u64* counts) {
+hipError_t launch_san_resolve(hipStream_t st, const DevPos& start, bool per_game, const DevPos* starts, DevPos* finals,
+                              const u32* tokens, u32 n_games, u32 n_plies, uint16_t* moves, u32* first_bad,
+                              u64* counts) {
   if (n_games == 0) return hipSuccess;
   if (n_plies && (!tokens || !moves)) return hipErrorInvalidValue;
-  Board b;
-  startpos_board(b);
-  hipLaunchKernelGGL(k_starts_san_resolve, dim3(blocks_for(n_games, kResolveBlock)), dim3(kResolveBlock), 0, st, b, 0u,
-                     (u32)pack_meta(15, -1), starts, finals, tokens, n_games, n_plies, moves, first_bad, counts);
-  return hipGetLastError();
-}
-
-hipError_t launch_san_resolve(hipStream_t st, const DevPos& start, const u32* tokens, u32 n_games, u32 n_plies,
-                              uint16_t* moves, u32* first_bad, u64* counts) {
-  if (n_games == 0) return hipSuccess;
-  if (n_plies && (!tokens || !moves)) return hipErrorInvalidValue;
+  const dim3 grid(blocks_for(n_games, kResolveBlock)), block(kResolveBlock);
   const Board b{start.bb[0], start.bb[1], start.bb[2], start.bb[3]};
-  hipLaunchKernelGGL(k_san_resolve, dim3(blocks_for(n_games, kResolveBlock)), dim3(kResolveBlock), 0, st, b,
-                     (u32)(start.stm & 1), (u32)pack_meta(start.castle, start.ep), tokens, n_games, n_plies, moves,
-                     first_bad, counts);
+  const u32 stm = start.stm & 1, meta = pack_meta(start.castle, start.ep);
+  if (per_game)
+    hipLaunchKernelGGL(k_starts_san_resolve, grid, block, 0, st, b, stm, meta, starts, finals, tokens, n_games,
+                       n_plies, moves, first_bad, counts);
+  else
+    hipLaunchKernelGGL(k_san_resolve, grid, block, 0, st, b, stm, meta, tokens, n_games, n_plies, moves, first_bad,
+                       counts);
   return hipGetLastError();
 }
 

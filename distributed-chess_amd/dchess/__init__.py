@@ -604,94 +604,9 @@ class Engine:
                                       _dptr(d_digests), C.byref(st)), "dc_replay_device")
         return {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
 
-    def replay_outcome(self, moves, start=None, start_halfmove=0, want_bitmap=True, want_digests=True):
-        """dc_replay_outcome (RULES_FIDE): replay that adjudicates every game.
-        moves: uint16 [n_plies, n_games] ply-major.  Returns (outcomes
-        OUTCOME_DTYPE [n_games], bitmap, digests, counts u64[GO_COUNT], stats dict)."""
-        moves = np.ascontiguousarray(moves, np.uint16)
-        n_plies, n_games = moves.shape
-        words = (n_games + 63) // 64
-        out = np.zeros(n_games, OUTCOME_DTYPE)
-        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
-        dig = np.zeros(n_games, np.uint64) if want_digests else None
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        sp = np.array([start], POS_DTYPE) if start is not None else None
-        _check(lib().dc_replay_outcome(self.ctx, _ptr(sp), int(start_halfmove), _ptr(moves), n_games, n_plies,
-                                       _ptr(out), _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st)),
-               "dc_replay_outcome")
-        return out, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
-
-    def replay_outcome_device(self, d_moves, n_games, n_plies, d_outcomes, d_bitmap=None, d_digests=None,
-                              start=None, start_halfmove=0):
-        """dc_replay_outcome_device on DeviceBuffers or raw device addresses
-        (d_outcomes: 8 bytes a game).  Returns (counts u64[GO_COUNT], stats dict)."""
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        sp = np.array([start], POS_DTYPE) if start is not None else None
-        _check(lib().dc_replay_outcome_device(self.ctx, _ptr(sp), int(start_halfmove), _dptr(d_moves), n_games,
-                                              n_plies, _dptr(d_outcomes), _dptr(d_bitmap), _dptr(d_digests),
-                                              _ptr(counts), C.byref(st)), "dc_replay_outcome_device")
-        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
-
-    def replay_san(self, moves, start=None, start_halfmove=0, want_bitmap=True, want_digests=True):
-        """dc_replay_san (RULES_FIDE): replay_outcome plus the SAN byte of every
-        ply.  moves: uint16 [n_plies, n_games] ply-major.  Returns (outcomes, san
-        uint8 [n_plies, n_games], bitmap, digests, counts u64[GO_COUNT], stats dict)."""
-        moves = np.ascontiguousarray(moves, np.uint16)
-        n_plies, n_games = moves.shape
-        words = (n_games + 63) // 64
-        out = np.zeros(n_games, OUTCOME_DTYPE)
-        san = np.zeros((n_plies, n_games), np.uint8)
-        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
-        dig = np.zeros(n_games, np.uint64) if want_digests else None
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        sp = np.array([start], POS_DTYPE) if start is not None else None
-        _check(lib().dc_replay_san(self.ctx, _ptr(sp), int(start_halfmove), _ptr(moves), n_games, n_plies,
-                                   _ptr(out), _ptr(san), _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st)),
-               "dc_replay_san")
-        return out, san, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
-
-    def replay_san_device(self, d_moves, n_games, n_plies, d_outcomes, d_san, d_bitmap=None, d_digests=None,
-                          start=None, start_halfmove=0):
-        """dc_replay_san_device on DeviceBuffers or raw device addresses (d_outcomes:
-        8 bytes a game, d_san: one byte a move).  Returns (counts u64[GO_COUNT], stats dict)."""
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        sp = np.array([start], POS_DTYPE) if start is not None else None
-        _check(lib().dc_replay_san_device(self.ctx, _ptr(sp), int(start_halfmove), _dptr(d_moves), n_games, n_plies,
-                                          _dptr(d_outcomes), _dptr(d_san), _dptr(d_bitmap), _dptr(d_digests),
-                                          _ptr(counts), C.byref(st)), "dc_replay_san_device")
-        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
-
-    def resolve_san(self, tokens, start=None, want_first_bad=True, want_counts=True):
-        """dc_san_resolve (RULES_FIDE): tokens uint32 [n_plies, n_games] ply-major
-        (SAN_TOKEN_NONE = no move) -> (moves uint16 [n_plies, n_games] with
-        MOVE_NOMATCH / MOVE_AMBIGUOUS / MOVE_MALFORMED where no single legal move
-        fits, first_bad uint32 [n_games], counts u64[SR_COUNT])."""
-        tokens = np.ascontiguousarray(tokens, np.uint32)
-        n_plies, n_games = tokens.shape
-        moves = np.zeros((n_plies, n_games), np.uint16)
-        first_bad = np.zeros(n_games, np.uint32) if want_first_bad else None
-        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
-        sp = np.array([start], POS_DTYPE) if start is not None else None
-        _check(lib().dc_san_resolve(self.ctx, _ptr(sp), _ptr(tokens), n_games, n_plies, _ptr(moves),
-                                    _ptr(first_bad), _ptr(counts)), "dc_san_resolve")
-        return moves, first_bad, counts
-
-    def resolve_san_device(self, d_tokens, n_games, n_plies, d_moves, d_first_bad=None, start=None,
-                           want_counts=True):
-        """dc_san_resolve_device on DeviceBuffers or raw device addresses (d_tokens:
-        4 bytes a ply, d_moves: 2, d_first_bad: 4 bytes a game or None).  Returns
-        counts u64[SR_COUNT] (None if not wanted)."""
-        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
-        sp = np.array([start], POS_DTYPE) if start is not None else None
-        _check(lib().dc_san_resolve_device(self.ctx, _ptr(sp), _dptr(d_tokens), n_games, n_plies, _dptr(d_moves),
-                                           _dptr(d_first_bad), _ptr(counts)), "dc_san_resolve_device")
-        return counts
-
-    # ---- the per-game-start forms: a start position and a half-move clock per game
+    # ---- adjudicating replay and SAN resolving.  A shared-start form passes start (a
+    # position or None) and, for a replay, start_halfmove; a *_starts form passes
+    # per_game = (starts, start_halfmoves, want_finals) or its device arrays.
     @staticmethod
     def _per_game(starts, start_halfmoves, n_games, want_finals):
         """The *_starts calls' per-game arrays: (starts, clocks, finals), each None or [n_games]."""
@@ -709,6 +624,104 @@ class Engine:
             hm = np.ascontiguousarray(h, np.uint16)
         return sp, hm, (np.zeros(n_games, POS_DTYPE) if want_finals else None)
 
+    def _replay_host(self, name, moves, want_san, want_bitmap, want_digests, start=None, start_halfmove=0,
+                     per_game=None):
+        """The four host replay forms: (outcomes, [san,] bitmap, digests, counts, stats dict[, finals])."""
+        moves = np.ascontiguousarray(moves, np.uint16)
+        n_plies, n_games = moves.shape
+        out = np.zeros(n_games, OUTCOME_DTYPE)
+        san = (np.zeros((n_plies, n_games), np.uint8),) if want_san else ()
+        bitmap = np.zeros((n_plies, (n_games + 63) // 64), np.uint64) if want_bitmap else None
+        dig = np.zeros(n_games, np.uint64) if want_digests else None
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        if per_game is None:
+            sp = np.array([start], POS_DTYPE) if start is not None else None
+            lead, finals = (_ptr(sp), int(start_halfmove)), ()
+        else:
+            sp, hm, fin = self._per_game(per_game[0], per_game[1], n_games, per_game[2])
+            lead, finals = (_ptr(sp), _ptr(hm)), (fin,)
+        _check(getattr(lib(), name)(self.ctx, *lead, _ptr(moves), n_games, n_plies, *map(_ptr, (out,) + san),
+                                    _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st), *map(_ptr, finals)), name)
+        return (out,) + san + (bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}) + finals
+
+    def _replay_device(self, name, lead, d_moves, n_games, n_plies, d_outs, d_finals=()):
+        """The four device replay forms; lead: what the C call takes between the
+        context and the moves.  Returns (counts u64[GO_COUNT], stats dict)."""
+        counts = np.zeros(GO_COUNT, np.uint64)
+        st = _Stats()
+        _check(getattr(lib(), name)(self.ctx, *lead, _dptr(d_moves), n_games, n_plies, *map(_dptr, d_outs),
+                                    _ptr(counts), C.byref(st), *map(_dptr, d_finals)), name)
+        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+
+    def _resolve_host(self, name, tokens, want_first_bad, want_counts, start=None, per_game=None):
+        """Both host resolve forms: (moves, first_bad, counts[, finals])."""
+        tokens = np.ascontiguousarray(tokens, np.uint32)
+        n_plies, n_games = tokens.shape
+        moves = np.zeros((n_plies, n_games), np.uint16)
+        first_bad = np.zeros(n_games, np.uint32) if want_first_bad else None
+        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
+        if per_game is None:
+            sp, finals = (np.array([start], POS_DTYPE) if start is not None else None), ()
+        else:
+            sp, _, fin = self._per_game(per_game[0], None, n_games, per_game[1])
+            finals = (fin,)
+        _check(getattr(lib(), name)(self.ctx, _ptr(sp), _ptr(tokens), n_games, n_plies, _ptr(moves), _ptr(first_bad),
+                                    _ptr(counts), *map(_ptr, finals)), name)
+        return (moves, first_bad, counts) + finals
+
+    def _resolve_device(self, name, start, d_tokens, n_games, n_plies, d_moves, d_first_bad, want_counts, d_finals=()):
+        """Both device resolve forms; start: a pointer.  Returns counts u64[SR_COUNT] (None if not wanted)."""
+        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
+        _check(getattr(lib(), name)(self.ctx, start, _dptr(d_tokens), n_games, n_plies, _dptr(d_moves),
+                                    _dptr(d_first_bad), _ptr(counts), *map(_dptr, d_finals)), name)
+        return counts
+
+    def replay_outcome(self, moves, start=None, start_halfmove=0, want_bitmap=True, want_digests=True):
+        """dc_replay_outcome (RULES_FIDE): replay that adjudicates every game.
+        moves: uint16 [n_plies, n_games] ply-major.  Returns (outcomes
+        OUTCOME_DTYPE [n_games], bitmap, digests, counts u64[GO_COUNT], stats dict)."""
+        return self._replay_host("dc_replay_outcome", moves, False, want_bitmap, want_digests, start, start_halfmove)
+
+    def replay_outcome_device(self, d_moves, n_games, n_plies, d_outcomes, d_bitmap=None, d_digests=None,
+                              start=None, start_halfmove=0):
+        """dc_replay_outcome_device on DeviceBuffers or raw device addresses
+        (d_outcomes: 8 bytes a game).  Returns (counts u64[GO_COUNT], stats dict)."""
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        return self._replay_device("dc_replay_outcome_device", (_ptr(sp), int(start_halfmove)), d_moves, n_games,
+                                   n_plies, (d_outcomes, d_bitmap, d_digests))
+
+    def replay_san(self, moves, start=None, start_halfmove=0, want_bitmap=True, want_digests=True):
+        """dc_replay_san (RULES_FIDE): replay_outcome plus the SAN byte of every
+        ply.  moves: uint16 [n_plies, n_games] ply-major.  Returns (outcomes, san
+        uint8 [n_plies, n_games], bitmap, digests, counts u64[GO_COUNT], stats dict)."""
+        return self._replay_host("dc_replay_san", moves, True, want_bitmap, want_digests, start, start_halfmove)
+
+    def replay_san_device(self, d_moves, n_games, n_plies, d_outcomes, d_san, d_bitmap=None, d_digests=None,
+                          start=None, start_halfmove=0):
+        """dc_replay_san_device on DeviceBuffers or raw device addresses (d_outcomes:
+        8 bytes a game, d_san: one byte a move).  Returns (counts u64[GO_COUNT], stats dict)."""
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        return self._replay_device("dc_replay_san_device", (_ptr(sp), int(start_halfmove)), d_moves, n_games, n_plies,
+                                   (d_outcomes, d_san, d_bitmap, d_digests))
+
+    def resolve_san(self, tokens, start=None, want_first_bad=True, want_counts=True):
+        """dc_san_resolve (RULES_FIDE): tokens uint32 [n_plies, n_games] ply-major
+        (SAN_TOKEN_NONE = no move) -> (moves uint16 [n_plies, n_games] with
+        MOVE_NOMATCH / MOVE_AMBIGUOUS / MOVE_MALFORMED where no single legal move
+        fits, first_bad uint32 [n_games], counts u64[SR_COUNT])."""
+        return self._resolve_host("dc_san_resolve", tokens, want_first_bad, want_counts, start)
+
+    def resolve_san_device(self, d_tokens, n_games, n_plies, d_moves, d_first_bad=None, start=None,
+                           want_counts=True):
+        """dc_san_resolve_device on DeviceBuffers or raw device addresses (d_tokens:
+        4 bytes a ply, d_moves: 2, d_first_bad: 4 bytes a game or None).  Returns
+        counts u64[SR_COUNT] (None if not wanted)."""
+        sp = np.array([start], POS_DTYPE) if start is not None else None
+        return self._resolve_device("dc_san_resolve_device", _ptr(sp), d_tokens, n_games, n_plies, d_moves,
+                                    d_first_bad, want_counts)
+
+    # ---- the per-game-start forms: a start position and a half-move clock per game
     def replay_outcome_starts(self, moves, starts=None, start_halfmoves=None, want_bitmap=True, want_digests=True,
                               want_finals=True):
         """dc_replay_outcome_starts: replay_outcome with game g starting from
@@ -716,88 +729,45 @@ class Engine:
         clock start_halfmoves[g] (None: 0).  Returns replay_outcome's tuple with
         finals appended: POS_DTYPE [n_games], the position every game stopped
         in (None if not wanted)."""
-        moves = np.ascontiguousarray(moves, np.uint16)
-        n_plies, n_games = moves.shape
-        words = (n_games + 63) // 64
-        sp, hm, finals = self._per_game(starts, start_halfmoves, n_games, want_finals)
-        out = np.zeros(n_games, OUTCOME_DTYPE)
-        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
-        dig = np.zeros(n_games, np.uint64) if want_digests else None
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        _check(lib().dc_replay_outcome_starts(self.ctx, _ptr(sp), _ptr(hm), _ptr(moves), n_games, n_plies, _ptr(out),
-                                              _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st), _ptr(finals)),
-               "dc_replay_outcome_starts")
-        return out, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}, finals
+        return self._replay_host("dc_replay_outcome_starts", moves, False, want_bitmap, want_digests,
+                                 per_game=(starts, start_halfmoves, want_finals))
 
     def replay_outcome_starts_device(self, d_moves, n_games, n_plies, d_outcomes, d_bitmap=None, d_digests=None,
                                      d_starts=None, d_start_halfmoves=None, d_finals=None):
         """dc_replay_outcome_starts_device on DeviceBuffers or raw device addresses
         (d_starts, d_finals: 40 bytes a game; d_start_halfmoves: 2).  Returns
         (counts u64[GO_COUNT], stats dict)."""
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        _check(lib().dc_replay_outcome_starts_device(self.ctx, _dptr(d_starts), _dptr(d_start_halfmoves),
-                                                     _dptr(d_moves), n_games, n_plies, _dptr(d_outcomes),
-                                                     _dptr(d_bitmap), _dptr(d_digests), _ptr(counts), C.byref(st),
-                                                     _dptr(d_finals)), "dc_replay_outcome_starts_device")
-        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+        return self._replay_device("dc_replay_outcome_starts_device", (_dptr(d_starts), _dptr(d_start_halfmoves)),
+                                   d_moves, n_games, n_plies, (d_outcomes, d_bitmap, d_digests), (d_finals,))
 
     def replay_san_starts(self, moves, starts=None, start_halfmoves=None, want_bitmap=True, want_digests=True,
                           want_finals=True):
         """dc_replay_san_starts: replay_san with per-game starts and clocks (as
         replay_outcome_starts).  Returns replay_san's tuple with finals appended."""
-        moves = np.ascontiguousarray(moves, np.uint16)
-        n_plies, n_games = moves.shape
-        words = (n_games + 63) // 64
-        sp, hm, finals = self._per_game(starts, start_halfmoves, n_games, want_finals)
-        out = np.zeros(n_games, OUTCOME_DTYPE)
-        san = np.zeros((n_plies, n_games), np.uint8)
-        bitmap = np.zeros((n_plies, words), np.uint64) if want_bitmap else None
-        dig = np.zeros(n_games, np.uint64) if want_digests else None
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        _check(lib().dc_replay_san_starts(self.ctx, _ptr(sp), _ptr(hm), _ptr(moves), n_games, n_plies, _ptr(out),
-                                          _ptr(san), _ptr(bitmap), _ptr(dig), _ptr(counts), C.byref(st),
-                                          _ptr(finals)), "dc_replay_san_starts")
-        return out, san, bitmap, dig, counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}, finals
+        return self._replay_host("dc_replay_san_starts", moves, True, want_bitmap, want_digests,
+                                 per_game=(starts, start_halfmoves, want_finals))
 
     def replay_san_starts_device(self, d_moves, n_games, n_plies, d_outcomes, d_san, d_bitmap=None, d_digests=None,
                                  d_starts=None, d_start_halfmoves=None, d_finals=None):
         """dc_replay_san_starts_device on DeviceBuffers or raw device addresses.
         Returns (counts u64[GO_COUNT], stats dict)."""
-        counts = np.zeros(GO_COUNT, np.uint64)
-        st = _Stats()
-        _check(lib().dc_replay_san_starts_device(self.ctx, _dptr(d_starts), _dptr(d_start_halfmoves), _dptr(d_moves),
-                                                 n_games, n_plies, _dptr(d_outcomes), _dptr(d_san), _dptr(d_bitmap),
-                                                 _dptr(d_digests), _ptr(counts), C.byref(st), _dptr(d_finals)),
-               "dc_replay_san_starts_device")
-        return counts, {k: int(getattr(st, k)) for k, _ in _Stats._fields_}
+        return self._replay_device("dc_replay_san_starts_device", (_dptr(d_starts), _dptr(d_start_halfmoves)),
+                                   d_moves, n_games, n_plies, (d_outcomes, d_san, d_bitmap, d_digests), (d_finals,))
 
     def resolve_san_starts(self, tokens, starts=None, want_first_bad=True, want_counts=True, want_finals=True):
         """dc_san_resolve_starts: resolve_san with game g starting from starts[g]
         (POS_DTYPE [n_games]; None: the start position).  Returns resolve_san's
         tuple with finals appended: the position after every game's last
         resolved move (None if not wanted)."""
-        tokens = np.ascontiguousarray(tokens, np.uint32)
-        n_plies, n_games = tokens.shape
-        sp, _, finals = self._per_game(starts, None, n_games, want_finals)
-        moves = np.zeros((n_plies, n_games), np.uint16)
-        first_bad = np.zeros(n_games, np.uint32) if want_first_bad else None
-        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
-        _check(lib().dc_san_resolve_starts(self.ctx, _ptr(sp), _ptr(tokens), n_games, n_plies, _ptr(moves),
-                                           _ptr(first_bad), _ptr(counts), _ptr(finals)), "dc_san_resolve_starts")
-        return moves, first_bad, counts, finals
+        return self._resolve_host("dc_san_resolve_starts", tokens, want_first_bad, want_counts,
+                                  per_game=(starts, want_finals))
 
     def resolve_san_starts_device(self, d_tokens, n_games, n_plies, d_moves, d_first_bad=None, d_starts=None,
                                   d_finals=None, want_counts=True):
         """dc_san_resolve_starts_device on DeviceBuffers or raw device addresses.
         Returns counts u64[SR_COUNT] (None if not wanted)."""
-        counts = np.zeros(SR_COUNT, np.uint64) if want_counts else None
-        _check(lib().dc_san_resolve_starts_device(self.ctx, _dptr(d_starts), _dptr(d_tokens), n_games, n_plies,
-                                                  _dptr(d_moves), _dptr(d_first_bad), _ptr(counts),
-                                                  _dptr(d_finals)), "dc_san_resolve_starts_device")
-        return counts
+        return self._resolve_device("dc_san_resolve_starts_device", _dptr(d_starts), d_tokens, n_games, n_plies,
+                                    d_moves, d_first_bad, want_counts, (d_finals,))
 
     def state_hash(self, moves, names, start=None, history=""):
         """keccak256(serde_json(final GameState)) of every game of a replay batch
