@@ -38,6 +38,7 @@
 
 #include "dc_common.h"
 #include "dc_hash.h"
+#include "dc_hash_digits.h"
 #include "dc_keccak.h"
 
 DC_BBPROF_DEFINE(hash)  // measurement builds only (tools/bbprof.py)
@@ -149,13 +150,6 @@ __device__ __forceinline__ u32 kind_index(u32 code) {
        : code == KC_K ? 5 : 6;
 }
 
-// a + 2 on 32-bit packed BCD (7 digits: callers keep the numbers below 10^7)
-__device__ __forceinline__ u32 bcd_add2(u32 a) {
-  const u32 t1 = a + 0x06666666u, t2 = t1 + 2, t3 = t1 ^ 2;
-  const u32 t5 = ~(t2 ^ t3) & 0x11111110u;  // the digits that carried
-  return t2 - ((t5 >> 2) | (t5 >> 3));
-}
-
 constexpr u32 kHashThreads = 256;
 // one token is at most 18 bytes (" " + 10 digits + ". " + kind + file + "x" +
 // square); 46 B holds three BCD-numbered ones (15 bytes each) or two of any kind
@@ -248,6 +242,8 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
   // digit loop were 5.8 % of the kernel's issue, tools/bbprof.py)
   // (32-bit: every number of the batch below bcd_max <= 10^7, else the divisions)
   const bool bcd_ok = (u64)hist_tokens + 2ull * n_plies + 1 < (u64)min(bcd_max, 10000000u);  // kernel-uniform
+  // (this loop stays here: as a helper beside bcd_add2 in dc_hash_digits.h the
+  // kernel came out 100 bytes longer, with four SGPR spills)
   u32 bcd = 0;
   if (bcd_ok)
     for (u32 v = hist_tokens + 1, sh = 0; v; v /= 10, sh += 4) bcd |= (v % 10) << sh;
@@ -339,22 +335,9 @@ __global__ __launch_bounds__(kHashThreads) void k_state_hash_ref(Board start, u3
             const u32 ki = info ? (code & 7u) : kind_index(nibble(b, f) >> 1);
             const bool cap = info ? (code & 8u) != 0 : ((occupied(b) >> t) & 1) != 0;
             if (ntok) mytok[n++] = ' ';
-            // N's decimal digits straight into the token from the BCD (round 4
-            // built them in a dynamically indexed register array: 29 % of the
-            // kernel's issue cycles in tools/bbprof.py's count)
-            if (bcd_ok) {
-              const u32 nd = max(1u, (35u - (u32)__clz((int)bcd)) >> 2);
-              for (u32 i = 0; i < nd; ++i) mytok[n + i] = (char)('0' + __builtin_amdgcn_ubfe(bcd, 4 * (nd - 1 - i), 4));
-              n += nd;
-            } else {  // digits written last-first
-              u32 v = ntok + 1, nd = 1;
-              for (u32 q = v; q >= 10; q /= 10) ++nd;
-              for (u32 i = nd; i-- > 0;) {
-                mytok[n + i] = (char)('0' + v % 10);
-                v /= 10;
-              }
-              n += nd;
-            }
+            // N's decimal digits straight into the token (dc_hash_digits.h)
+            if (bcd_ok) n += bcd_emit(mytok + n, bcd);
+            else n += div_emit(mytok + n, ntok + 1);
             mytok[n++] = '.';
             mytok[n++] = ' ';
             if (ki != 0) mytok[n++] = "PNBRQK"[ki];

@@ -38,6 +38,36 @@ def test_host_keccak_matches_oracle():
         assert dchess.keccak256(d) == S.keccak256(d), n
 
 
+def test_host_keccak_every_length_to_300():
+    """Every fill of the 136-byte rate, twice over: the 0x01 .. 0x80 padding
+    at each position, 0x81 in one byte at 135 and 271, the extra all-padding
+    block at 0, 136 and 272."""
+    d = np.random.default_rng(4).integers(0, 256, 300, dtype=np.uint8).tobytes()
+    for n in range(301):
+        assert dchess.keccak256(d[:n]) == S.keccak256(d[:n]), n
+
+
+# Unicode White_Space (Rust's char::is_whitespace, chess.rs:169-175) ...
+WHITE_SPACE = ([0x20, 0x85, 0xA0, 0x1680, 0x2028, 0x2029, 0x202F, 0x205F, 0x3000]
+               + list(range(0x09, 0x0E)) + list(range(0x2000, 0x200B)))
+# ... and what is not: Python's str.split() splits at U+001C-U+001F, U+200B is
+# a format character, U+180E left White_Space in Unicode 6.3
+NOT_WHITE_SPACE = [0x1C, 0x1D, 0x1E, 0x1F, 0x200B, 0x180E]
+
+
+@pytest.mark.parametrize("cp", WHITE_SPACE + NOT_WHITE_SPACE, ids=lambda cp: "U+%04X" % cp)
+def test_history_token_count_is_rusts_white_space(cp):
+    """update_history numbers a move 1 + split_whitespace().count(): the host
+    (dc_history_append, the count dc_state_hash hands its kernel) and the
+    oracle agree on "a" + ch + "b" + one move, for every White_Space
+    character and for the near misses."""
+    start = "a" + chr(cp) + "b"
+    mv, info = np.array([12 | 28 << 6], np.uint16), np.array([0], np.uint8)  # e2e4: a pawn, no capture
+    want = start + (" 3. e4" if cp in WHITE_SPACE else " 2. e4")
+    assert S.append_history(start, "e4") == want
+    assert dchess.history_append(start, mv, info) == want
+
+
 NAMES = ["Alice", "Bob", 'q"uo\\te', "tab\tnew\nline\x01\x1f", "Ümlaut ♞ 名前", ""]
 
 
@@ -72,26 +102,40 @@ def test_unknown_kind_string_serialised():
 
 
 # ------------------------------------------------------------------- GPU
-def _oracle_hashes(start, history, names, mv):
-    """Move-by-move: refcpu verdicts (chess.rs:82-125), apply (chess.rs:72-77),
-    update_history (chess.rs:127-184), serde_json, keccak256."""
+def _oracle_walk(start, history, col):
+    """One game move by move: refcpu verdicts (chess.rs:82-125), apply
+    (chess.rs:72-77), update_history (chess.rs:127-184).  Yields (n, stm,
+    history, cells, event) for n = 0 .. len(col): the state after the first n
+    plies (cells is the walk's own array: copy it to keep it) and what ply
+    n - 1 did: None for n = 0 and for a rejected ply, else (kind, capture)."""
     import oracle_lib as O
+    cells, stm, hist = start.cells.copy(), start.stm, history
+    yield 0, stm, hist, cells, None
+    for p in range(len(col)):
+        m, ev = int(col[p]), None
+        f, t = m & 63, (m >> 6) & 63
+        if (m != O.SENTINEL and not m & 0x8000
+                and O.ref_validate(cells, stm, f >> 3, f & 7, t >> 3, t & 7) == O.OK):
+            ev = (int(cells[f]) & 7, bool(cells[t] >= 0))
+            hist = S.append_history(hist, S.notation(S.KIND[ev[0]], ev[1], f, t))
+            cells[t], cells[f] = cells[f], -1
+            stm ^= 1
+        yield p + 1, stm, hist, cells, ev
+
+
+def _oracle_hash(stm, names, hist, cells):
+    """serde_json, keccak256 of one final state, as a uint8[32] row."""
+    return np.frombuffer(S.keccak256(S.game_state_json(stm, names[0], names[1], hist, cells).encode()), np.uint8)
+
+
+def _oracle_hashes(start, history, names, mv):
+    """Every game walked move by move (_oracle_walk), then serde_json, keccak256."""
     n_plies, n_games = mv.shape
     out = np.zeros((n_games, 32), np.uint8)
     for g in range(n_games):
-        cells, stm, hist = start.cells.copy(), start.stm, history
-        for p in range(n_plies):
-            m = int(mv[p, g])
-            if m == O.SENTINEL or m & 0x8000:
-                continue
-            f, t = m & 63, (m >> 6) & 63
-            if O.ref_validate(cells, stm, f >> 3, f & 7, t >> 3, t & 7) != O.OK:
-                continue
-            hist = S.append_history(hist, S.notation(S.KIND[cells[f] & 7], cells[t] >= 0, f, t))
-            cells[t], cells[f] = cells[f], -1
-            stm ^= 1
-        w, b = names[g]
-        out[g] = np.frombuffer(S.keccak256(S.game_state_json(stm, w, b, hist, cells).encode()), np.uint8)
+        for _, stm, hist, cells, _ in _oracle_walk(start, history, mv[:, g]):
+            pass
+        out[g] = _oracle_hash(stm, names[g], hist, cells)
     return out
 
 
